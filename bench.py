@@ -33,6 +33,12 @@ ratio: above 1 it is flagged in model_ratios_above_1).  For the BVH walk also it
 instructions, L2 hit rate and, with the diagnostic counter build (build.py build_trav_stats), the
 walk's lane counters (scripts/trav_stats.py).
 The scan kernel is measured separately at n = 2^28 (8 B/element, 2 GiB, beyond the 256 MiB MALL).
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline figure needs: set-up, W
+warm-up steps, the N timed steps, the result line.  Everything else above — the profiled segment and
+the roofline, the --pmc passes, the walk counters, the scan and compaction kernels, the CPU baselines
+and the drop-in leg — runs with --full only (where the --no-* options still switch single legs off).
+--dump-outputs DIR writes what the timed path handed back in its last step (_dump_outputs).
 """
 from __future__ import annotations
 
@@ -429,11 +435,50 @@ def _walk_counters(scene_path, spp_pass, timeout=300) -> dict | None:
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: everything written stays below this
+DUMP_SAMPLE_PIXELS = 4 << 20   # a larger image is sampled: 4 Mi pixels x 3 x f32 = 48 MiB
+DUMP_SAMPLE_SEED = 20240607
+
+
+def _dump_outputs(out_dir, image: np.ndarray, bounce_live) -> dict:
+    """--dump-outputs: what a caller of the timed path receives after its last step.
+      image.npy        the framebuffer accumulator copied out at the end of the timed region (the sum
+                       of radiance over every iteration since the context was created, warm-up
+                       included), float32 (H, W, 3) — or, where that exceeds the size limit, the
+                       (DUMP_SAMPLE_PIXELS, 3) pixels at the sorted flat indices
+                       default_rng(DUMP_SAMPLE_SEED).choice(H * W, DUMP_SAMPLE_PIXELS, replace=False):
+                       the same pixels in every run of the same arguments;
+      bounce_live.npy  paths alive at each bounce over the timed steps (pt.stats()), float64 (DEPTH,).
+    The scene, the camera and the iteration numbers are fixed by the arguments and the RNG is keyed by
+    (iteration, pixel, depth), so two runs with the same arguments write the same arrays."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    sampled = False
+    if img.nbytes > DUMP_MAX_BYTES - (1 << 20):
+        flat = img.reshape(-1, 3)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+        img, sampled = np.ascontiguousarray(flat[idx]), True
+    live = np.asarray(bounce_live, dtype=np.float64)
+    assert img.nbytes + live.nbytes <= DUMP_MAX_BYTES
+    np.save(out_dir / "image.npy", img)
+    np.save(out_dir / "bounce_live.npy", live)
+    return {"dir": str(out_dir), "files": ["image.npy", "bounce_live.npy"], "image_shape": list(img.shape),
+            "image_sampled": sampled, "bytes": int(img.nbytes + live.nbytes)}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side leg: the profiled segment and the roofline, the rocprofv3 --pmc "
+                         "passes, the walk counters, the scan and compaction kernels, the CPU baselines and the "
+                         "drop-in leg (a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (the framebuffer of the last step, the "
+                         "paths alive per bounce) as DIR/<name>.npy; identical from run to run with the same arguments")
     ap.add_argument("--scan-n", type=int, default=1 << 28)
     ap.add_argument("--scan-reps", type=int, default=20)
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -577,22 +622,34 @@ def main() -> None:
     if dist is not None:   # the last rank to arrive waits least: its gather time is the collective's own
         gather_ms_min = -D.max_over_ranks(torch, dist, -gather_ms, dev)
 
-    # Kernel-level timing for the roofline: a profiled segment of the same workload right after
-    # the timed region (HIP events bracket every launch on its stream; events inside the timed
-    # region would add inter-kernel gaps to `value`).
-    prof_passes = min(args.steps * passes_per_step, 50)
-    pt.profile(True)
-    pt.profile_read()
-    sp0 = pt.stats()
-    for _ in range(prof_passes):
-        pt.render_pass(it, stream)
-        it += spp
-    prof = pt.profile_read()
-    pt.profile(False)
-    sp1 = pt.stats()
-
     seg = s1["segments"] - s0["segments"]
     live = [b - a for a, b in zip(s0["bounce_live"], s1["bounce_live"])]
+    # the image the timed region handed back: the rank's tile at N = 1, the gathered tiles on rank 0
+    full_image = None
+    if rank == 0 and rows_all is not None:
+        full_image = D.assemble([t.cpu().numpy() for t in rows_all], scene.camera().res[1], world)
+        assert np.isfinite(full_image).all()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = _dump_outputs(args.dump_outputs, full_image if full_image is not None else tile.cpu().numpy(), live)
+        _log(rank, f"[bench] wrote {dumped['files']} ({dumped['bytes']} bytes) to {dumped['dir']}")
+
+    # Kernel-level timing for the roofline (--full): a profiled segment of the same workload right
+    # after the timed region (HIP events bracket every launch on its stream; events inside the timed
+    # region would add inter-kernel gaps to `value`).
+    prof = None
+    if args.full:
+        prof_passes = min(args.steps * passes_per_step, 50)
+        pt.profile(True)
+        pt.profile_read()
+        sp0 = pt.stats()
+        for _ in range(prof_passes):
+            pt.render_pass(it, stream)
+            it += spp
+        prof = pt.profile_read()
+        pt.profile(False)
+        sp1 = pt.stats()
+
     t_max = elapsed
     seg_all = seg
     ranks = None
@@ -604,96 +661,97 @@ def main() -> None:
         ranks = D.rank_spread(D.per_rank(torch, dist, (elapsed, seg), dev))
         ranks["gather_ms_per_rank"] = [r[0] for r in D.per_rank(torch, dist, (gather_ms,), dev)]
 
-    # roofline of the dominant kernel (bounces >= 1), over the profiled segment
     depth = st_r.traceDepth
-    plive = [b - a for a, b in zip(sp0["bounce_live"], sp1["bounce_live"])]
-    pemit = [b - a for a, b in zip(sp0["bounce_emit"], sp1["bounce_emit"])]
-    seg_bounce = sum(plive[1:depth])
-    sorted_ = bool(gui.sortbyMaterial)
-    b_ms, b_n, b_busy = prof["bounce"]
-    if sorted_:   # material-sorted pipeline: every producer after the first + its histogram scans
-        b_ms, b_n, b_busy = prof["sort"]
-    t_ms, t_n, t_busy = prof["traverse"]
-    walk = t_n > 0   # mesh scene with the BVH walk in its own kernel (k_traverse / k_traverse4)
-    f_ms, f_n, _ = prof["first_bounce"]
-    mesh = scene.counts()[2] > 0
-    quads = walk and not args.bvh_cull and os.environ.get("PT_AMD_TRAV") != "pairs" and \
-        _native_lib().pt_scene_bvh_quads(scene.handle, None, 0, None, None) > 0
-    # k_bounce<FIRST, SPP1, MESH mode>: mesh scenes run mode 2 (closest mesh hit from k_traverse)
-    bprefix = f"k_bounce<false, {'true' if spp == 1 else 'false'}, {2 if mesh else 0}>"
-    # (k_traverse4<FIRST, K>: K triangle tasks per lane, 2, or 1 where the exact t-cull is on)
-    wprefix = "k_traverse4<false," if quads else "k_traverse<false>"
-    kprefix = wprefix if walk else bprefix
-    kernel_name = ("material-sorted pipeline (k_sort_produce: shade + compact + intersect / histogram scan + permutation)"
-                   if sorted_ else ("k_traverse4<false, K>" if kprefix == "k_traverse4<false," else kprefix))
-    kernel_min = 0
-    for b in range(1, depth):
-        n_out = plive[b + 1] if b + 1 < depth else 0
-        kernel_min += PATH_BYTES * plive[b] + PATH_BYTES * n_out + FB_RMW_BYTES * pemit[b]
-    k_ms, k_n, k_busy = (t_ms, t_n, t_busy) if walk else (b_ms, b_n, b_busy)
-    per_launch_bytes = SEGMENT_BYTES * seg_bounce / max(k_n, 1)
-    avg_ms = k_ms / max(k_n, 1)
-    # The lanes' launches overlap (two streams), so a launch's own duration is shared with the other
-    # lane's work: launches x avg_ms exceeds the step.  The kernel's time per launch that fits the
-    # step is the union of its launch intervals / launches (launches x eff_ms = union <= the step):
-    # that is the roofline's duration; the HIP-event average (= rocprofv3's) is reported beside it.
-    eff_ms = k_busy / max(k_n, 1) if k_busy > 0 else avg_ms
-    achieved = per_launch_bytes / (eff_ms * 1e-3) / 1e9 if eff_ms > 0 else 0.0
-    achieved_overlapped = per_launch_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-    # pt_kernels.hip pt_create: 3 lanes for large sorted passes (kThreeLanePaths), 1 with the BVH walk
-    default_lanes = 3 if sorted_ and pt.npaths >= (48 << 20) else (1 if quads else 2)
-    lanes = min(int(os.environ.get("PT_AMD_LANES", str(default_lanes))), spp, 4) \
-        if (spp > 1 and (sorted_ or os.environ.get("PT_PIPELINE") != "split")) else 1
-    # every bounce's algorithmic bytes (184 B per segment) of one step over the step time: the
-    # byte metric at step level (near 1.0 it is saturated and stops being evidence; VALU issue is
-    # the limiter then, roofline.valu_issue)
-    step_seg = seg / max(args.steps, 1)
-    prof_steps = prof_passes / max(passes_per_step, 1)
-    roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                "definition": "184 B (SURVEY.md §8d) x segments per launch / the kernel's time per launch "
-                              "(union of its launch intervals over the profiled passes / launches, HIP events "
-                              "on the launch streams: launches x that time fits the step)",
-                "kernel": kernel_name, "effective_launch_ms": eff_ms, "avg_launch_ms": avg_ms, "launches": k_n,
-                "lanes": lanes,
-                "launches_per_step": k_n / max(prof_steps, 1e-9),
-                "kernel_ms_per_step": k_busy / max(prof_steps, 1e-9),
-                "overlapped": {"avg_launch_ms": avg_ms, "achieved": achieved_overlapped,
-                               "frac": achieved_overlapped / HBM_PEAK_GBS,
-                               "definition": "the same bytes / the HIP-event average launch duration (= rocprofv3 "
-                                             "--kernel-trace --stats' average; each launch shares the GPU with the "
-                                             "other lane's, so launches x this exceeds the step)"},
-                "segments_per_launch": seg_bounce / max(k_n, 1),
-                "algorithmic_bytes_per_launch": per_launch_bytes,
-                "step_model_ratio": SEGMENT_BYTES * step_seg / (elapsed / max(args.steps, 1)) / 1e9 / HBM_PEAK_GBS
-                if world == 1 else None,
-                "step_model_ratio_definition": "§8d model bytes (184 B x traced segments of one step, all bounces) / "
-                                               "ms_per_step / 8 TB/s — a model ratio, not a measured HBM fraction",
-                # two lanes' launches overlap: the same bytes over the union of the launch intervals
-                "aggregate": {"busy_ms": k_busy,
-                              "achieved": SEGMENT_BYTES * seg_bounce / (k_busy * 1e-3) / 1e9 if k_busy > 0 else 0.0,
-                              "frac": SEGMENT_BYTES * seg_bounce / (k_busy * 1e-3) / 1e9 / HBM_PEAK_GBS
-                              if k_busy > 0 else 0.0,
-                              "definition": "184 B x segments of bounces >= 1 / union of their launch intervals"}}
-    if not walk:
-        roofline["kernel_min_bytes_per_launch"] = kernel_min / max(b_n, 1)
-    else:   # the bounce kernel after the walk (bounded closest hit with the mesh hit + shade + compact)
-        bb = SEGMENT_BYTES * seg_bounce / max(b_n, 1)
-        b_avg = b_ms / max(b_n, 1)
-        roofline["bounce_kernel"] = {
-            "kernel": bprefix, "avg_launch_ms": b_avg, "launches": b_n,
-            "achieved": bb / (b_avg * 1e-3) / 1e9 if b_avg > 0 else 0.0,
-            "frac": bb / (b_avg * 1e-3) / 1e9 / HBM_PEAK_GBS if b_avg > 0 else 0.0,
-            "kernel_min_bytes_per_launch": kernel_min / max(b_n, 1)}
-        roofline["walk_share_of_gpu_time"] = t_ms / max(t_ms + b_ms + f_ms + prof["first_traverse"][0], 1e-9)
-        roofline["walk_info"] = walk_info   # 4-wide walk, its exact t-cull on/off, share of slots it can cull
-        roofline["first_traverse_avg_ms"] = prof["first_traverse"][0] / max(prof["first_traverse"][1], 1)
+    roofline = first_bounce_avg_ms = None
+    if args.full:   # roofline of the dominant kernel (bounces >= 1), over the profiled segment
+        plive = [b - a for a, b in zip(sp0["bounce_live"], sp1["bounce_live"])]
+        pemit = [b - a for a, b in zip(sp0["bounce_emit"], sp1["bounce_emit"])]
+        seg_bounce = sum(plive[1:depth])
+        sorted_ = bool(gui.sortbyMaterial)
+        b_ms, b_n, b_busy = prof["bounce"]
+        if sorted_:   # material-sorted pipeline: every producer after the first + its histogram scans
+            b_ms, b_n, b_busy = prof["sort"]
+        t_ms, t_n, t_busy = prof["traverse"]
+        walk = t_n > 0   # mesh scene with the BVH walk in its own kernel (k_traverse / k_traverse4)
+        f_ms, f_n, _ = prof["first_bounce"]
+        first_bounce_avg_ms = f_ms / max(f_n, 1)
+        mesh = scene.counts()[2] > 0
+        quads = walk and not args.bvh_cull and os.environ.get("PT_AMD_TRAV") != "pairs" and \
+            _native_lib().pt_scene_bvh_quads(scene.handle, None, 0, None, None) > 0
+        # k_bounce<FIRST, SPP1, MESH mode>: mesh scenes run mode 2 (closest mesh hit from k_traverse)
+        bprefix = f"k_bounce<false, {'true' if spp == 1 else 'false'}, {2 if mesh else 0}>"
+        # (k_traverse4<FIRST, K>: K triangle tasks per lane, 2, or 1 where the exact t-cull is on)
+        wprefix = "k_traverse4<false," if quads else "k_traverse<false>"
+        kprefix = wprefix if walk else bprefix
+        kernel_name = ("material-sorted pipeline (k_sort_produce: shade + compact + intersect / histogram scan + "
+                       "permutation)"
+                       if sorted_ else ("k_traverse4<false, K>" if kprefix == "k_traverse4<false," else kprefix))
+        kernel_min = 0
+        for b in range(1, depth):
+            n_out = plive[b + 1] if b + 1 < depth else 0
+            kernel_min += PATH_BYTES * plive[b] + PATH_BYTES * n_out + FB_RMW_BYTES * pemit[b]
+        k_ms, k_n, k_busy = (t_ms, t_n, t_busy) if walk else (b_ms, b_n, b_busy)
+        per_launch_bytes = SEGMENT_BYTES * seg_bounce / max(k_n, 1)
+        avg_ms = k_ms / max(k_n, 1)
+        # The lanes' launches overlap (two streams), so a launch's own duration is shared with the other
+        # lane's work: launches x avg_ms exceeds the step.  The kernel's time per launch that fits the
+        # step is the union of its launch intervals / launches (launches x eff_ms = union <= the step):
+        # that is the roofline's duration; the HIP-event average (= rocprofv3's) is reported beside it.
+        eff_ms = k_busy / max(k_n, 1) if k_busy > 0 else avg_ms
+        achieved = per_launch_bytes / (eff_ms * 1e-3) / 1e9 if eff_ms > 0 else 0.0
+        achieved_overlapped = per_launch_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+        # pt_kernels.hip pt_create: 3 lanes for large sorted passes (kThreeLanePaths), 1 with the BVH walk
+        default_lanes = 3 if sorted_ and pt.npaths >= (48 << 20) else (1 if quads else 2)
+        lanes = min(int(os.environ.get("PT_AMD_LANES", str(default_lanes))), spp, 4) \
+            if (spp > 1 and (sorted_ or os.environ.get("PT_PIPELINE") != "split")) else 1
+        # every bounce's algorithmic bytes (184 B per segment) of one step over the step time: the
+        # byte metric at step level (near 1.0 it is saturated and stops being evidence; VALU issue is
+        # the limiter then, roofline.valu_issue)
+        step_seg = seg / max(args.steps, 1)
+        prof_steps = prof_passes / max(passes_per_step, 1)
+        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                    "definition": "184 B (SURVEY.md §8d) x segments per launch / the kernel's time per launch "
+                                  "(union of its launch intervals over the profiled passes / launches, HIP events "
+                                  "on the launch streams: launches x that time fits the step)",
+                    "kernel": kernel_name, "effective_launch_ms": eff_ms, "avg_launch_ms": avg_ms, "launches": k_n,
+                    "lanes": lanes,
+                    "launches_per_step": k_n / max(prof_steps, 1e-9),
+                    "kernel_ms_per_step": k_busy / max(prof_steps, 1e-9),
+                    "overlapped": {"avg_launch_ms": avg_ms, "achieved": achieved_overlapped,
+                                   "frac": achieved_overlapped / HBM_PEAK_GBS,
+                                   "definition": "the same bytes / the HIP-event average launch duration (= rocprofv3 "
+                                                 "--kernel-trace --stats' average; each launch shares the GPU with "
+                                                 "the other lane's, so launches x this exceeds the step)"},
+                    "segments_per_launch": seg_bounce / max(k_n, 1),
+                    "algorithmic_bytes_per_launch": per_launch_bytes,
+                    "step_model_ratio": SEGMENT_BYTES * step_seg / (elapsed / max(args.steps, 1)) / 1e9 / HBM_PEAK_GBS
+                    if world == 1 else None,
+                    "step_model_ratio_definition": "§8d model bytes (184 B x traced segments of one step, all "
+                                                   "bounces) / ms_per_step / 8 TB/s — a model ratio, not a measured "
+                                                   "HBM fraction",
+                    # two lanes' launches overlap: the same bytes over the union of the launch intervals
+                    "aggregate": {"busy_ms": k_busy,
+                                  "achieved": SEGMENT_BYTES * seg_bounce / (k_busy * 1e-3) / 1e9 if k_busy > 0 else 0.0,
+                                  "frac": SEGMENT_BYTES * seg_bounce / (k_busy * 1e-3) / 1e9 / HBM_PEAK_GBS
+                                  if k_busy > 0 else 0.0,
+                                  "definition": "184 B x segments of bounces >= 1 / union of their launch intervals"}}
+        if not walk:
+            roofline["kernel_min_bytes_per_launch"] = kernel_min / max(b_n, 1)
+        else:   # the bounce kernel after the walk (bounded closest hit with the mesh hit + shade + compact)
+            bb = SEGMENT_BYTES * seg_bounce / max(b_n, 1)
+            b_avg = b_ms / max(b_n, 1)
+            roofline["bounce_kernel"] = {
+                "kernel": bprefix, "avg_launch_ms": b_avg, "launches": b_n,
+                "achieved": bb / (b_avg * 1e-3) / 1e9 if b_avg > 0 else 0.0,
+                "frac": bb / (b_avg * 1e-3) / 1e9 / HBM_PEAK_GBS if b_avg > 0 else 0.0,
+                "kernel_min_bytes_per_launch": kernel_min / max(b_n, 1)}
+            roofline["walk_share_of_gpu_time"] = t_ms / max(t_ms + b_ms + f_ms + prof["first_traverse"][0], 1e-9)
+            roofline["walk_info"] = walk_info   # 4-wide walk, its exact t-cull on/off, share of slots it can cull
+            roofline["first_traverse_avg_ms"] = prof["first_traverse"][0] / max(prof["first_traverse"][1], 1)
 
     result = None
     if rank == 0:
-        if rows_all is not None:
-            full = D.assemble([t.cpu().numpy() for t in rows_all], scene.camera().res[1], world)
-            assert np.isfinite(full).all()
         if world > 1:   # the N-GPU line's parts (the driver's scaling run): every rank's segments, the gather
             assert gather_ms is not None and gather_ms_min is not None, "N > 1: the tile gather was not timed"
             assert seg_all >= seg > 0 and rows_all is not None and len(rows_all) == world, \
@@ -737,15 +795,17 @@ def main() -> None:
             "nominal_mrays": scene.camera().res[0] * scene.camera().res[1] * (args.samples if strong else spp * world)
             * depth / (t_max / args.steps) / 1e6,
             "nominal_definition": "W x H x samples per step x DEPTH / ms_per_step (no early termination counted)",
-            "first_bounce_avg_ms": f_ms / max(f_n, 1),
+            "first_bounce_avg_ms": first_bounce_avg_ms,
             "gather_ms": gather_ms,
             "gather_ms_last_rank": gather_ms_min,
             "ranks": ranks,
+            "full": bool(args.full),
+            "outputs": dumped,
         }
-        if not args.no_scan:
+        if args.full and not args.no_scan:
             result["scan"] = scan_bench(torch, dev, args.scan_n, args.scan_reps)
             result["compact"] = compact_bench(torch, dev, args.scan_n, max(3, args.scan_reps // 2))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline_render(args.cpu_seconds)
             # labelled multithreaded variant: 16 host threads (the box's CPU share per GPU)
             result["cpu_baseline_mt"] = cpu_baseline_render_mt(args.cpu_seconds / 2, min(16, os.cpu_count() or 1))
@@ -758,13 +818,13 @@ def main() -> None:
         dist.barrier()
         dist.destroy_process_group()
     pt.free()
-    if rank == 0 and world == 1 and not args.no_dropin and not shard_of and args.config == "cornell":
+    if args.full and rank == 0 and world == 1 and not args.no_dropin and not shard_of and args.config == "cornell":
         try:
             result["dropin"] = dropin_bench(scene_path)
             result["dropin"]["vs_batched"] = result["dropin"]["value"] / result["value"]
         except Exception as e:   # a reported side leg: never fail the bench line
             result["dropin"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_pmc:
+    if args.full and rank == 0 and world == 1 and not args.no_pmc:
         try:
             extra = _pmc_leg(args, scene_path, spp, sorted_, eff_ms, kprefix, seg_bounce / max(k_n, 1), k_busy, k_n,
                              walk=walk)
@@ -775,9 +835,9 @@ def main() -> None:
             lps = roofline["launches"] / max(prof_passes, 1) * passes_per_step   # launches per step
             roofline["isolated"]["launches_per_step"] = lps
             roofline["isolated"]["ms_per_step_if_serial"] = lps * roofline["isolated"]["avg_launch_ms"]
-    if rank == 0 and world == 1 and walk and not args.no_walk_counters:
+    if args.full and rank == 0 and world == 1 and walk and not args.no_walk_counters:
         roofline["walk_counters"] = _walk_counters(scene_path, spp)
-    if rank == 0:
+    if args.full and rank == 0:
         _finalize_roofline(roofline)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -21,7 +21,7 @@ for step in ${STEPS:-tests bench ktrace}; do
         ${PYTEST_K:+-k "$PYTEST_K"} > "$O/pytest_gpu.log" 2>&1; rc=$?
     echo "pytest rc=$rc"; tail -3 "$O/pytest_gpu.log"; [ $rc -eq 0 ] || exit 1 ;;
   bench)
-    timeout -k 10 900 python -u bench.py ${BENCH_ARGS:-} > "$O/bench.json" 2> "$O/bench.log"; rc=$?
+    timeout -k 10 900 python -u bench.py --full ${BENCH_ARGS:-} > "$O/bench.json" 2> "$O/bench.log"; rc=$?
     echo "bench rc=$rc"; [ $rc -eq 0 ] || { tail -20 "$O/bench.log"; exit 1; }
     cp gpurun_out/bench_pmc/summary.json "$O/bench_pmc_summary.json" 2>/dev/null
     python3 -c "
@@ -31,7 +31,7 @@ print('  hbm', {k: round(v['frac'],3) for k, v in r.get('hbm', {}).items() if is
 print('  dropin', d.get('dropin', {}).get('value'), 'scan GB/s', d.get('scan', {}).get('GB/s'), 'cpu', d.get('cpu_baseline', {}).get('value'))" ;;
   ktrace)
     ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/ktrace" -o run -- \
-        python3 "$R/bench.py" --no-pmc --no-cpu-baseline --no-dropin --steps 20 ${BENCH_ARGS:-} > "$O/ktrace_bench.json" 2> "$O/ktrace_bench.log" ); rc=$?
+        python3 "$R/bench.py" --full --no-pmc --no-cpu-baseline --no-dropin --steps 20 ${BENCH_ARGS:-} > "$O/ktrace_bench.json" 2> "$O/ktrace_bench.log" ); rc=$?
     echo "ktrace rc=$rc"; [ $rc -eq 0 ] || exit 1
     find "$O/ktrace" -name "*kernel_stats.csv" -exec cp {} "$O/kernel_stats.csv" \;
     head -8 "$O/kernel_stats.csv"
@@ -44,7 +44,7 @@ print('  dropin', d.get('dropin', {}).get('value'), 'scan GB/s', d.get('scan', {
     for c in "cornell_hd_sorted --steps 10" "multi_object_4k --steps 5" "random_triangles_100k --steps 2" \
              "tessellated_meshes_100k --steps 3"; do
       set -- $c
-      timeout -k 10 400 python bench.py --config $c --warmup 2 --no-cpu-baseline --no-scan \
+      timeout -k 10 400 python bench.py --full --config $c --warmup 2 --no-cpu-baseline --no-scan \
           >> "$O/configs.jsonl" 2> "$O/config_$1.err" || { echo "config $1 failed"; tail -5 "$O/config_$1.err"; exit 1; }
       cp gpurun_out/bench_pmc/summary.json "$O/pmc_$1.json" 2>/dev/null
     done
@@ -57,7 +57,7 @@ for l in open('$O/configs.jsonl'):
     for k in $(seq 1 ${RUNS:-3}); do
       for v in new ${VARIANTS:-base}; do
         if [ $v = new ]; then unset PT_AMD_LIB; else export PT_AMD_LIB=$R/cuda_pathtracer_amd/build/libpt_amd_$v.so; fi
-        timeout -k 10 300 python -u bench.py --steps ${AB_STEPS:-20} --warmup 3 --no-cpu-baseline --no-scan --no-pmc --no-dropin ${BENCH_ARGS:-} \
+        timeout -k 10 300 python -u bench.py --full --steps ${AB_STEPS:-20} --warmup 3 --no-cpu-baseline --no-scan --no-pmc --no-dropin ${BENCH_ARGS:-} \
             > "$O/ab_${v}_$k.json" 2> "$O/ab_${v}_$k.err" || { echo "bench $v failed"; tail -5 "$O/ab_${v}_$k.err"; exit 1; }
         python3 -c "import json;d=json.load(open('$O/ab_${v}_$k.json'));r=d['roofline'];print('$v', round(d['value'],1), round(d['ms_per_step'],3), 'eff', round(r['effective_launch_ms']*1e3,1), 'us; first', round(d.get('first_bounce_avg_ms',0)*1e3,1))"
       done

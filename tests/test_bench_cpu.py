@@ -57,6 +57,36 @@ def test_without_counters_the_model_is_labelled():
     assert r["model_ratios_above_1"] == {}
 
 
+def test_dump_outputs_writes_a_small_image_whole(tmp_path):
+    import numpy as np
+    import bench
+    img = np.random.default_rng(3).random((37, 53, 3), dtype=np.float32)
+    live = [640000, 500001, 3]
+    info = bench._dump_outputs(tmp_path / "out", img, live)
+    got = np.load(tmp_path / "out" / "image.npy")
+    assert got.dtype == np.float32 and got.tobytes() == img.tobytes() and got.shape == (37, 53, 3)
+    gl = np.load(tmp_path / "out" / "bounce_live.npy")
+    assert gl.dtype == np.float64 and gl.tolist() == [640000.0, 500001.0, 3.0]
+    assert not info["image_sampled"] and sorted(p.name for p in (tmp_path / "out").iterdir()) == sorted(info["files"])
+
+
+def test_dump_outputs_samples_a_large_image_the_same_way_every_time(tmp_path):
+    """A 4K framebuffer (95 MiB) is over the 64 MiB limit: a fixed, seeded sample of its pixels."""
+    import numpy as np
+    import bench
+    h, w = 2160, 3840
+    img = (np.arange(h * w * 3, dtype=np.int64) % 8191).astype(np.float32).reshape(h, w, 3)
+    a = bench._dump_outputs(tmp_path / "a", img, [1, 2])
+    b = bench._dump_outputs(tmp_path / "b", img.copy(), [1, 2])
+    ga, gb = np.load(tmp_path / "a" / "image.npy"), np.load(tmp_path / "b" / "image.npy")
+    assert a["image_sampled"] and ga.dtype == np.float32 and ga.shape == (bench.DUMP_SAMPLE_PIXELS, 3)
+    assert ga.tobytes() == gb.tobytes() and a["image_shape"] == b["image_shape"]
+    total = sum(p.stat().st_size for p in (tmp_path / "a").iterdir())
+    assert total <= 64 << 20
+    idx = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(h * w, bench.DUMP_SAMPLE_PIXELS, replace=False))
+    assert np.array_equal(ga, img.reshape(-1, 3)[idx])
+
+
 def test_fractions_above_one_are_listed():
     import bench
     r = _line(traffic=1e9, valu=1e9)
