@@ -73,6 +73,19 @@ class Stats(C.Structure):
                 ("bound_mismatch", C.c_uint32)]
 
 
+class DenoiseParams(C.Structure):
+    """pt_denoise_params; DenoiseParams.default() = pt_denoise_params_default."""
+    _fields_ = [("levels", C.c_int32), ("sigma_c", C.c_float), ("sigma_n", C.c_float), ("sigma_p", C.c_float),
+                ("demodulate", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    @classmethod
+    def default(cls) -> "DenoiseParams":
+        p = cls()
+        lib().pt_denoise_params_default(C.byref(p))
+        return p
+
+
+assert C.sizeof(DenoiseParams) == 32
 assert C.sizeof(Geom) == 272 and C.sizeof(Material) == 48 and C.sizeof(Triangle) == 124
 assert C.sizeof(BvhNode) == 40
 
@@ -165,6 +178,14 @@ SIGNATURES = {
     "pt_encode_hdr": (_I, [_P, _I, _I, _F, _P, C.c_int64, _P]),
     "pt_set_accum": (_I, [_P, _P]),
     "pt_decode_jpeg": (_I, [C.c_char_p, C.c_int64, _IP, _IP, _IP, _P, C.c_int64]),
+    "pt_gbuffer": (_I, [_P, _P, _P, _P, _P, _P]),
+    "pt_get_gbuffer": (_I, [_P, _P, _P, _P, _P]),
+    "pt_denoise_params_default": (None, [C.POINTER(DenoiseParams)]),
+    "pt_denoiser_create": (_I, [_I, _I, C.POINTER(_P)]),
+    "pt_denoiser_destroy": (_I, [_P]),
+    "pt_denoiser_run": (_I, [_P, _P, _F, _P, _P, _P, C.POINTER(DenoiseParams), _P, _P]),
+    "pt_denoise_host": (_I, [_I, _I, _P, _F, _P, _P, _P, C.POINTER(DenoiseParams), _P]),
+    "pt_denoise_image": (_I, [_P, _F, C.POINTER(DenoiseParams), _P]),
 }
 
 _lib = None

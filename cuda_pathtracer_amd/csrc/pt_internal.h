@@ -52,5 +52,7 @@ int build_bvh_device(Scene& S, double* ms);
 int decode_jpeg(const uint8_t* data, size_t size, int32_t* width, int32_t* height, int32_t* components,
                 std::vector<uint8_t>* pixels);
 int load_texture_file(TextureHost& t);
+// Denoiser (pt_denoise.hip): the argument checks of pt_denoiser_run that need no device
+int denoise_check(const pt_denoise_params* p, float samples);
 
 }  // namespace pt

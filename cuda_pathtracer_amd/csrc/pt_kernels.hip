@@ -1382,6 +1382,43 @@ __global__ __launch_bounds__(kBlock) void k_trace(const KArgs A) {
     flush_emissive(A, emit_cnt, &s_cnt);
 }
 
+// First-hit feature planes of the tile (pt_gbuffer), one tile pixel per lane, in pt_get_image's pixel
+// order.  The ray is the deterministic camera ray (the host clears fl.ssaa and fl.dof, so raygen_at
+// draws nothing), the hit the plain closest hit; runs once per camera, not per sample.
+//   gA = (n, mat bits), gB = (point_on_ray(o, d, t), t), alb = the factor a diffuse first bounce
+// multiplies into the throughput (shade_from: texture-or-colour, times colour unless single_albedo;
+// (1, 1, 1) for emissive materials and misses), uv = the hit's texture coordinates (optional).
+// A miss: mat -1, t -1, everything else 0.
+template <bool MESH>
+__global__ __launch_bounds__(kBlock) void k_gbuffer(const KArgs A, v4f* __restrict__ gA, v4f* __restrict__ gB,
+                                                    v4f* __restrict__ alb, v2f* __restrict__ uv) {
+    const int npix = A.tile.npix;
+    for (int lp = blockIdx.x * kBlock + (int)threadIdx.x; lp < npix; lp += gridDim.x * kBlock) {
+        PathReg p;
+        raygen_at(A.cam, A.fl, A.tile, lp, 0, lp, p);
+        const Hit h = intersect_scene<MESH>(A.S, A.fl, p.o, p.d);
+        v4f a = {0.f, 0.f, 0.f, __int_as_float(-1)}, b = {0.f, 0.f, 0.f, -1.0f}, c = {1.f, 1.f, 1.f, 0.f};
+        v2f t = {0.f, 0.f};
+        if (h.t > 0.0f) {
+            const f3 P = point_on_ray(p.o, p.d, h.t);
+            a = v4f{h.n.x, h.n.y, h.n.z, __int_as_float(h.mat)};
+            b = v4f{P.x, P.y, P.z, h.t};
+            t = v2f{h.u, h.v};
+            const DMaterial& m = A.S.mats[h.mat];
+            if (!(m.emittance > 0.0f)) {
+                const f3 mcol = F3(m.color[0], m.color[1], m.color[2]);
+                f3 k = m.texture_id != -1 ? tex_color(A.S.texs[m.texture_id], h.u, h.v) : mcol;
+                if (!A.fl.single_albedo) k = hadamard(k, mcol);
+                c = v4f{k.x, k.y, k.z, 0.f};
+            }
+        }
+        gA[lp] = a;
+        gB[lp] = b;
+        alb[lp] = c;
+        if (uv) uv[lp] = t;
+    }
+}
+
 // Split pipeline, batched passes: the first dense index of every batch iteration present (the
 // compacted array is iteration-major because the compaction is stable and slots are too).
 __global__ __launch_bounds__(kBlock) void k_iter_bases(const KArgs A) {
@@ -4951,6 +4988,73 @@ int pt_copy_image(pt_ctx* c, float* d_rgb, void* stream) {
     HIP_TRY(hipMemcpyAsync(d_rgb, c->args.image, (size_t)c->args.tile.npix * 3 * sizeof(float),
                            hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return mark_ctx(c, (hipStream_t)stream);
+}
+
+// The first-hit feature planes of the tile (k_gbuffer), ordered like pt_copy_image: after the context's
+// queued work (a pt_set_flags in between has synchronised by itself), and marked as its last work.
+int pt_gbuffer(pt_ctx* c, float* d_gA, float* d_gB, float* d_alb, float* d_uv, void* stream) {
+    if (!c || !d_gA || !d_gB || !d_alb) return pt::fail(PT_ERR_ARG, "null argument");
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = wait_finalize(c, st)) return rc;
+    KArgs A = c->args;
+    A.fl.ssaa = 0;   // the deterministic camera ray: no jitter, no lens
+    A.fl.dof = 0;
+    A.tile.iter_first = 0;
+    const int npix = A.tile.npix;
+    const dim3 grid(std::min((npix + kBlock - 1) / kBlock, 16384));
+    auto kern = A.S.ntris > 0 ? k_gbuffer<true> : k_gbuffer<false>;
+    hipLaunchKernelGGL(kern, grid, dim3(kBlock), 0, st, A, (v4f*)d_gA, (v4f*)d_gB, (v4f*)d_alb, (v2f*)d_uv);
+    HIP_TRY(hipGetLastError());
+    return mark_ctx(c, st);
+}
+
+int pt_get_gbuffer(pt_ctx* c, float* h_gA, float* h_gB, float* h_alb, float* h_uv) {
+    if (!c || !h_gA || !h_gB || !h_alb) return pt::fail(PT_ERR_ARG, "null argument");
+    const size_t npix = (size_t)c->args.tile.npix;
+    float* d = nullptr;   // gA | gB | alb | uv
+    if (hipMalloc((void**)&d, npix * 14 * sizeof(float)) != hipSuccess) return pt::fail(PT_ERR_NOMEM, "hipMalloc (G-buffer)");
+    int rc = pt_gbuffer(c, d, d + 4 * npix, d + 8 * npix, h_uv ? d + 12 * npix : nullptr, c->io_stream);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        float* dst[4] = {h_gA, h_gB, h_alb, h_uv};
+        const size_t off[5] = {0, 4 * npix, 8 * npix, 12 * npix, 14 * npix};
+        for (int k = 0; k < 4 && e == hipSuccess; ++k)
+            if (dst[k]) e = hipMemcpyAsync(dst[k], d + off[k], (off[k + 1] - off[k]) * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
+        const hipError_t e2 = hipStreamSynchronize(c->io_stream);
+        if (e == hipSuccess) e = e2;
+    }
+    (void)hipFree(d);
+    if (rc) return rc;
+    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_get_gbuffer: ") + hipGetErrorString(e));
+    return PT_OK;
+}
+
+// G-buffer + accumulator -> denoised host image: everything on the context's io stream, the filter
+// reading the accumulator in place (it is not modified).
+int pt_denoise_image(pt_ctx* c, float samples, const pt_denoise_params* prm, float* host_out_rgb) {
+    if (!c || !host_out_rgb) return pt::fail(PT_ERR_ARG, "null argument");
+    if (c->args.tile.world > 1) return pt::fail(PT_ERR_ARG, "pt_denoise_image needs the whole image (world == 1)");
+    if (int rc = pt::denoise_check(prm, samples)) return rc;
+    const int W = c->args.tile.W;
+    const size_t npix = (size_t)c->args.tile.npix;
+    float* d = nullptr;   // gA | gB | alb | out
+    if (hipMalloc((void**)&d, npix * 15 * sizeof(float)) != hipSuccess) return pt::fail(PT_ERR_NOMEM, "hipMalloc (denoise)");
+    pt_denoiser* dn = nullptr;
+    int rc = pt_denoiser_create(W, (int32_t)(npix / W), &dn);
+    if (!rc) rc = pt_gbuffer(c, d, d + 4 * npix, d + 8 * npix, nullptr, c->io_stream);
+    if (!rc) rc = pt_denoiser_run(dn, c->args.image, samples, d, d + 4 * npix, d + 8 * npix, prm, d + 12 * npix, c->io_stream);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        rc = mark_ctx(c, c->io_stream);
+        e = hipMemcpyAsync(host_out_rgb, d + 12 * npix, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(c->io_stream);
+    if (e == hipSuccess) e = e2;
+    pt_denoiser_destroy(dn);
+    (void)hipFree(d);
+    if (rc) return rc;
+    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_denoise_image: ") + hipGetErrorString(e));
+    return PT_OK;
 }
 
 int pt_reset_image(pt_ctx* c, void* stream) {

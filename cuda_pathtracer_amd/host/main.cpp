@@ -3,7 +3,10 @@
 // window — pathtraceInit, `iterations` calls of pathtrace(), saveImage() (main.cpp:88-112) and
 // pathtraceFree().  The camera is the first-frame orbit recompute (done by pt_scene_finalize).
 //
-//   pathtracer_amd SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr]
+//   pathtracer_amd SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise] [--aov DIR]
+// --denoise also writes the a-trous-filtered image (pt_denoise_image) as ...samp.denoised.png (and
+// .denoised.hdr with --hdr); --aov DIR writes the first-hit G-buffer planes (pt_get_gbuffer) as raw
+// little-endian float32 files with a one-line JSON sidecar of their shapes.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +14,7 @@
 #include <ctime>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "pathtrace.h"
 
@@ -25,21 +29,62 @@ std::string currentTimeString() {   // preview.cpp:21-28
 }
 
 // saveImage (main.cpp:88-112): divide by the sample count, mirror x, clamp, x255, PNG.
+// `denoised`: a per-sample image to write instead (as ...samp.denoised.png / .hdr).
 std::string saveImage(const Scene& scene, const std::string& dir, const std::string& start, int iteration,
-                      bool hdr = false) {
+                      bool hdr = false, const float* denoised = nullptr) {
     const float samples = (float)iteration;
     std::ostringstream ss;
     ss << scene.state.imageName << "." << start << "." << samples << "samp";
     std::string filename = ss.str();
     if (!dir.empty()) filename = dir + "/" + filename;
+    if (denoised) filename += ".denoised";
     filename += hdr ? ".hdr" : ".png";   // Image::savePNG / saveHDR append the extension (image.cpp:22-49)
     const int W = scene.state.camera.res[0], H = scene.state.camera.res[1];
-    const float* rgb = reinterpret_cast<const float*>(scene.state.image.data());
-    if (hdr ? pt_save_hdr(filename.c_str(), rgb, W, H, samples) : pt_save_png(filename.c_str(), rgb, W, H, samples)) {
+    const float* rgb = denoised ? denoised : reinterpret_cast<const float*>(scene.state.image.data());
+    const float div = denoised ? 1.0f : samples;
+    if (hdr ? pt_save_hdr(filename.c_str(), rgb, W, H, div) : pt_save_png(filename.c_str(), rgb, W, H, div)) {
         std::fprintf(stderr, "saveImage: %s\n", pt_last_error());
         std::exit(EXIT_FAILURE);
     }
     return filename;
+}
+
+void writeFloats(const std::string& path, const std::vector<float>& v) {
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f || std::fwrite(v.data(), sizeof(float), v.size(), f) != v.size() || std::fclose(f)) {
+        std::fprintf(stderr, "error: cannot write %s\n", path.c_str());
+        std::exit(EXIT_FAILURE);
+    }
+}
+
+// --aov: gA (normal, material id bits), gB (position, t), albedo, uv as DIR/<imageName>.<plane>.f32
+void saveAovs(const Scene& scene, const std::string& dir) {
+    const int W = scene.state.camera.res[0], H = scene.state.camera.res[1];
+    const size_t n = (size_t)W * H;
+    std::vector<float> gA(4 * n), gB(4 * n), alb(4 * n), uv(2 * n);
+    if (pt_get_gbuffer(pathtraceContext(), gA.data(), gB.data(), alb.data(), uv.data())) {
+        std::fprintf(stderr, "error: G-buffer: %s\n", pt_last_error());
+        std::exit(EXIT_FAILURE);
+    }
+    const std::string base = dir + "/" + scene.state.imageName;
+    writeFloats(base + ".gA.f32", gA);
+    writeFloats(base + ".gB.f32", gB);
+    writeFloats(base + ".albedo.f32", alb);
+    writeFloats(base + ".uv.f32", uv);
+    FILE* f = std::fopen((base + ".aov.json").c_str(), "w");
+    if (!f) {
+        std::fprintf(stderr, "error: cannot write %s.aov.json\n", base.c_str());
+        std::exit(EXIT_FAILURE);
+    }
+    const char* names[4] = {"gA", "gB", "albedo", "uv"};
+    const int chans[4] = {4, 4, 4, 2};
+    std::fprintf(f, "{\"dtype\": \"<f4\", \"planes\": {");
+    for (int k = 0; k < 4; ++k)
+        std::fprintf(f, "%s\"%s\": {\"file\": \"%s.%s.f32\", \"shape\": [%d, %d, %d]}", k ? ", " : "", names[k],
+                     scene.state.imageName.c_str(), names[k], H, W, chans[k]);
+    std::fprintf(f, "}}\n");
+    std::fclose(f);
+    std::printf("wrote %s.{gA,gB,albedo,uv}.f32 and %s.aov.json\n", base.c_str(), base.c_str());
 }
 
 }  // namespace
@@ -47,19 +92,22 @@ std::string saveImage(const Scene& scene, const std::string& dir, const std::str
 int main(int argc, char** argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2) {
-        std::printf("Usage: %s SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr]\n", argv[0]);
+        std::printf("Usage: %s SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise] "
+                    "[--aov DIR]\n", argv[0]);
         return 1;
     }
     const char* sceneFile = argv[1];
     int iterations = -1;
-    std::string out_dir;
-    bool sort = false, png = true, hdr = false;
+    std::string out_dir, aov_dir;
+    bool sort = false, png = true, hdr = false, denoise = false, aov = false;
     for (int i = 2; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--iterations") && i + 1 < argc) iterations = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out_dir = argv[++i];
         else if (!std::strcmp(argv[i], "--sort")) sort = true;
         else if (!std::strcmp(argv[i], "--no-png")) png = false;
         else if (!std::strcmp(argv[i], "--hdr")) hdr = true;   // also write the saveHDR .hdr file
+        else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
+        else if (!std::strcmp(argv[i], "--aov") && i + 1 < argc) { aov_dir = argv[++i]; aov = true; }
         else {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
             return 1;
@@ -86,6 +134,18 @@ int main(int argc, char** argv) {
                 scene->state.camera.res[0], scene->state.camera.res[1], scene->state.traceDepth, secs);
     if (png) std::printf("wrote %s\n", saveImage(*scene, out_dir, startTimeString, iteration).c_str());
     if (hdr) std::printf("wrote %s\n", saveImage(*scene, out_dir, startTimeString, iteration, true).c_str());
+    if (denoise) {
+        std::vector<float> dn((size_t)scene->state.camera.res[0] * scene->state.camera.res[1] * 3);
+        pt_denoise_params prm;
+        pt_denoise_params_default(&prm);
+        if (pt_denoise_image(pathtraceContext(), (float)iteration, &prm, dn.data())) {
+            std::fprintf(stderr, "error: denoise: %s\n", pt_last_error());
+            return EXIT_FAILURE;
+        }
+        std::printf("wrote %s\n", saveImage(*scene, out_dir, startTimeString, iteration, false, dn.data()).c_str());
+        if (hdr) std::printf("wrote %s\n", saveImage(*scene, out_dir, startTimeString, iteration, true, dn.data()).c_str());
+    }
+    if (aov) saveAovs(*scene, aov_dir);
     pathtraceFree();
     delete guiData;
     delete scene;

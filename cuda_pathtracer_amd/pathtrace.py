@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._native import check_pt, lib
+from ._native import DenoiseParams, check_pt, lib  # noqa: F401
 
 SPHERE, CUBE, MESH = 0, 1, 2
 
@@ -369,6 +369,26 @@ class PathTracer:
     def preview_rgba(self, iteration: int, dst_ptr: int, stream=None) -> None:
         check_pt(lib().pt_preview_rgba(self._h, int(iteration), C.c_void_p(dst_ptr), _stream_ptr(stream)))
 
+    def gbuffer(self) -> dict:
+        """First-hit feature planes of the tile (pt_get_gbuffer; the deterministic camera ray): normal
+        (rows, W, 3), mat (rows, W) int32 with -1 on a miss, position (rows, W, 3), t (rows, W) with -1
+        on a miss, albedo (rows, W, 3) and uv (rows, W, 2)."""
+        r, w = self.rows, self.width
+        ga, gb, al = (np.empty((r, w, 4), np.float32) for _ in range(3))
+        uv = np.empty((r, w, 2), np.float32)
+        check_pt(lib().pt_get_gbuffer(self._h, ga.ctypes.data, gb.ctypes.data, al.ctypes.data, uv.ctypes.data))
+        return {"normal": ga[..., :3].copy(), "mat": ga[..., 3].copy().view(np.int32), "position": gb[..., :3].copy(),
+                "t": gb[..., 3].copy(), "albedo": al[..., :3].copy(), "uv": uv}
+
+    def denoised(self, samples: float, params: "N.DenoiseParams | None" = None) -> np.ndarray:
+        """The accumulator of `samples` samples filtered by the edge-avoiding a-trous denoiser over this
+        context's G-buffer (pt_denoise_image; world == 1 only): (H, W, 3) float32, per-sample radiance
+        (tonemap(..., 1.0) writes it).  The accumulator is not modified."""
+        prm = params if params is not None else N.DenoiseParams.default()
+        out = np.empty((self.rows, self.width, 3), np.float32)
+        check_pt(lib().pt_denoise_image(self._h, float(samples), C.byref(prm), out.ctypes.data))
+        return out
+
     def stats(self) -> dict:
         s = N.Stats()
         check_pt(lib().pt_stats(self._h, C.byref(s)))
@@ -394,6 +414,29 @@ class PathTracer:
         n = (C.c_uint64 * k)()
         check_pt(lib().pt_profile_read_kinds(self._h, k, ms, busy, n))
         return {name: (float(ms[i]), int(n[i]), float(busy[i])) for i, name in enumerate(self.KINDS)}
+
+
+def _plane4(xyz: np.ndarray, w: np.ndarray, shape) -> np.ndarray:
+    out = np.empty(shape + (4,), np.float32)
+    out[..., :3] = np.asarray(xyz, np.float32).reshape(shape + (3,))
+    out[..., 3] = np.asarray(w).reshape(shape)
+    return out
+
+
+def denoise(image: np.ndarray, samples: float, gbuffer: dict, params: "N.DenoiseParams | None" = None) -> np.ndarray:
+    """pt_denoise_host: filter an accumulated (H, W, 3) image of `samples` samples with the planes of
+    PathTracer.gbuffer() (normal, mat, position, t, albedo) -> (H, W, 3) float32 per-sample radiance."""
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    shape = img.shape[:2]
+    mat = np.ascontiguousarray(gbuffer["mat"], dtype=np.int32).view(np.float32)
+    ga = _plane4(gbuffer["normal"], mat, shape)
+    gb = _plane4(gbuffer["position"], np.asarray(gbuffer["t"], np.float32), shape)
+    al = _plane4(gbuffer["albedo"], np.zeros(shape, np.float32), shape)
+    prm = params if params is not None else N.DenoiseParams.default()
+    out = np.empty(shape + (3,), np.float32)
+    check_pt(lib().pt_denoise_host(shape[1], shape[0], img.ctypes.data, float(samples), ga.ctypes.data, gb.ctypes.data,
+                                   al.ctypes.data, C.byref(prm), out.ctypes.data))
+    return out
 
 
 def tonemap(image: np.ndarray, samples: float) -> np.ndarray:
@@ -429,8 +472,9 @@ def save_image_hdr(path: str, image: np.ndarray, samples: float) -> str:
 
 
 def render(scene_path: str, iterations: int | None = None, out_dir: str | None = None,
-           gui: GuiDataContainer | None = None) -> tuple[np.ndarray, str | None]:
-    """Headless runCuda loop (main.cpp:114-168): ITERATIONS passes, then saveImage."""
+           gui: GuiDataContainer | None = None, denoise: bool = False) -> tuple[np.ndarray, str | None]:
+    """Headless runCuda loop (main.cpp:114-168): ITERATIONS passes, then saveImage.  denoise=True
+    additionally saves FILE.<UTC>.<spp>samp.denoised.png (PathTracer.denoised); the raw PNG is the same."""
     scene = Scene(scene_path)
     st = scene.state()
     iters = iterations if iterations is not None else st.iterations
@@ -443,6 +487,8 @@ def render(scene_path: str, iterations: int | None = None, out_dir: str | None =
         stamp = time.strftime("%Y-%m-%d_%H-%M-%Sz", time.gmtime())
         path = str(Path(out_dir) / f"{st.imageName}.{stamp}.{iters}samp.png")
         save_image(path, img, iters)
+        if denoise:
+            save_image(path[:-len(".png")] + ".denoised.png", pt.denoised(iters), 1.0)
     pt.free()
     return img, path
 

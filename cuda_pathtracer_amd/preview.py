@@ -33,7 +33,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .pathtrace import GuiDataContainer, PathTracer, Scene, save_image
+from .pathtrace import GuiDataContainer, PathTracer, Scene, save_image, tonemap
 
 F32 = np.float32
 PI = F32(3.1415926535897932384626422832795028841971)   # utilities.h PI (a float)
@@ -90,6 +90,7 @@ class PreviewSession:
         self._factory = tracer_factory or (lambda sc, g: PathTracer(sc, g))
         self._read = read_preview or self._device_preview
         self._dbuf = None
+        self.denoise = False         # panel: show the a-trous-filtered image (PathTracer.denoised)
         self.lock = threading.RLock()
 
     # ---- callbacks (main.cpp:189-271) --------------------------------------------------------
@@ -146,7 +147,9 @@ class PreviewSession:
         """An edit in the panel (preview.cpp:243-271).  The general settings apply to the next
         iteration; the visual ones restart the accumulation (visual_settings_changed)."""
         with self.lock:
-            if name in GENERAL_SETTINGS or name in ("SSAA", "DoF"):
+            if name == "denoise":   # display only: the accumulation, saving and S are untouched
+                self.denoise = bool(value)
+            elif name in GENERAL_SETTINGS or name in ("SSAA", "DoF"):
                 setattr(self.gui, name, bool(value))
             elif name in SLIDERS:
                 lo, hi = SLIDERS[name]
@@ -175,7 +178,7 @@ class PreviewSession:
                 # pathtrace(pbo, frame, iteration): InitDataContainer's flags, one iteration, the PBO
                 self.ctx.set_flags(self.gui)
                 self.ctx.render_pass(self.iteration)
-                self.rgba = self._read(self.ctx, self.iteration)
+                self.rgba = self._denoised_preview() if self.denoise else self._read(self.ctx, self.iteration)
             else:
                 self.save_image()
                 self._free()
@@ -190,6 +193,14 @@ class PreviewSession:
             self._dbuf = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device="cuda")
         ctx.preview_rgba(it, self._dbuf.data_ptr())   # (the render's stream: NULL)
         return self._dbuf.cpu().numpy()
+
+    def _denoised_preview(self) -> np.ndarray:
+        """The PBO contents of the denoised image: the tonemapped bytes, un-mirrored back into the
+        PBO's pixel order (display_rgb mirrors x), alpha 0 as sendImageToPBO leaves it."""
+        rgb = tonemap(self.ctx.denoised(float(self.iteration)), 1.0)[:, ::-1]
+        out = np.zeros((self.height, self.width, 4), np.uint8)
+        out[..., :3] = rgb
+        return out
 
     def _free(self) -> None:
         if self.ctx is not None:
@@ -231,7 +242,8 @@ class PreviewSession:
                 "done": self.done, "closed": self.should_close,
                 "traced_depth": self.traced_depth,   # "Traced Depth %d"
                 "ms_per_frame": ft * 1e3, "fps": (1.0 / ft) if ft > 0 else 0.0,
-                "settings": {k: getattr(self.gui, k) for k in GENERAL_SETTINGS + VISUAL_SETTINGS},
+                "settings": {**{k: getattr(self.gui, k) for k in GENERAL_SETTINGS + VISUAL_SETTINGS},
+                             "denoise": self.denoise},
                 "camera": {"phi": float(self.phi), "theta": float(self.theta), "zoom": float(self.zoom),
                            "look_at": [float(v) for v in self.look_at],
                            "position": [float(v) for v in cam.position[:3]]},
@@ -275,7 +287,8 @@ fieldset{border:1px solid #555;margin:0 0 8px 0} input[type=range]{width:160px}<
 <fieldset><legend>General settings</legend>
 <label><input type="checkbox" id="russianRoulette"> Russian roulette</label><br>
 <label><input type="checkbox" id="sortbyMaterial"> Sort by material (can harm performance)</label><br>
-<label><input type="checkbox" id="useThrustPartition"> Use thrust library for path termination</label></fieldset>
+<label><input type="checkbox" id="useThrustPartition"> Use thrust library for path termination</label><br>
+<label><input type="checkbox" id="denoise"> Show the denoised image (edge-avoiding a-trous filter)</label></fieldset>
 <fieldset><legend>Visual settings</legend>
 <label><input type="checkbox" id="SSAA"> Enable stochastic sampled antialiasing</label><br>
 <label><input type="checkbox" id="DoF"> Enable DoF effects</label><br>
@@ -294,7 +307,7 @@ img.addEventListener('mousemove',e=>{const p=pos(e);post({kind:'move',x:p.x,y:p.
 img.addEventListener('contextmenu',e=>e.preventDefault());
 window.addEventListener('keydown',e=>{const k=e.key==='Escape'?'ESCAPE':e.key===' '?'SPACE':e.key.toUpperCase();
  if(['ESCAPE','SPACE','S'].includes(k)){e.preventDefault();post({kind:'key',key:k});}});
-for(const id of ['russianRoulette','sortbyMaterial','useThrustPartition','SSAA','DoF'])
+for(const id of ['russianRoulette','sortbyMaterial','useThrustPartition','denoise','SSAA','DoF'])
  document.getElementById(id).addEventListener('change',e=>post({kind:'setting',name:id,value:e.target.checked}));
 for(const id of ['aperture','focal_len'])
  document.getElementById(id).addEventListener('input',e=>post({kind:'setting',name:id,value:parseFloat(e.target.value)}));

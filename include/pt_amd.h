@@ -366,6 +366,47 @@ int pt_save_hdr(const char* path, const float* rgb, int32_t width, int32_t heigh
 int pt_encode_hdr(const float* rgb, int32_t width, int32_t height, float samples, uint8_t* out, int64_t cap,
                   int64_t* size);
 
+/* ---- first-hit G-buffer and denoiser ----------------------------------------------------- */
+/* Feature planes of the first hit of the deterministic camera ray (ssaa and dof off, whatever the
+ * context's flags), for this context's tile, in pt_get_image's pixel order (npix entries each):
+ *   gA  float4: n.x, n.y, n.z, material id as int32 bits; a miss has n = 0 and id -1
+ *   gB  float4: P.x, P.y, P.z, t; P = the point shading scatters from (getPointOnRay), t the hit
+ *               distance; a miss has P = 0 and t = -1
+ *   alb float4: r, g, b, 0: the factor a diffuse first bounce multiplies into the throughput
+ *               (texture-or-colour times colour, or texture-or-colour alone with single_albedo);
+ *               (1, 1, 1) for emissive materials and misses
+ *   uv  float2: the hit's texture coordinates, 0 on a miss (may be NULL)
+ * pt_gbuffer is asynchronous on `stream` (device pointers) and orders itself against the context's
+ * other work like pt_copy_image; pt_get_gbuffer fills host arrays and synchronises.  Any rank /
+ * world / spp. */
+int pt_gbuffer(pt_ctx* c, float* d_gA, float* d_gB, float* d_alb, float* d_uv, void* stream);
+int pt_get_gbuffer(pt_ctx* c, float* h_gA, float* h_gB, float* h_alb, float* h_uv);
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by gA / gB, on the colour
+ * divided by alb (demodulate) — the exact fp32 definition is DESIGN.md §10.  `levels` in 0..8 (step
+ * 2^i at level i; sigma_c halves per level), sigmas finite and > 0.  NaN inputs propagate. */
+typedef struct pt_denoise_params {
+    int32_t levels;               /* default 5 */
+    float sigma_c, sigma_n, sigma_p; /* colour (per-sample, demodulated), normal, plane distance; defaults 1, 0.3, 0.2 */
+    int32_t demodulate;           /* default 1 */
+    int32_t reserved[3];
+} pt_denoise_params;
+void pt_denoise_params_default(pt_denoise_params* p);
+typedef struct pt_denoiser pt_denoiser;
+int pt_denoiser_create(int32_t width, int32_t height, pt_denoiser** out);   /* owns two float4 planes */
+int pt_denoiser_destroy(pt_denoiser* d);
+/* Asynchronous on `stream`, device pointers.  d_rgb: accumulated W*H float3 of `samples` samples;
+ * d_out_rgb: per-sample W*H float3 (pt_tonemap(out, W, H, 1.0f, ...) writes it); must not alias d_rgb.
+ * Argument errors (PT_ERR_ARG) are found before any device call. */
+int pt_denoiser_run(pt_denoiser* d, const float* d_rgb, float samples, const float* d_gA, const float* d_gB,
+                    const float* d_alb, const pt_denoise_params* p, float* d_out_rgb, void* stream);
+/* The same on host arrays: allocates, copies, runs, copies back (synchronous). */
+int pt_denoise_host(int32_t width, int32_t height, const float* rgb, float samples, const float* gA,
+                    const float* gB, const float* alb, const pt_denoise_params* p, float* out_rgb);
+/* G-buffer + accumulator of a world == 1 context -> denoised host image (W*H float3, per sample).
+ * PT_ERR_ARG when world > 1.  The accumulator is not modified.  Synchronous. */
+int pt_denoise_image(pt_ctx* c, float samples, const pt_denoise_params* p, float* host_out_rgb);
+
 #ifdef __cplusplus
 }
 #endif
