@@ -150,6 +150,7 @@ SIGNATURES = {
     "pt_destroy": (_I, [_P]),
     "pt_set_flags": (_I, [_P, C.POINTER(Flags)]),
     "pt_ctx_cmask_info": (_I, [_P, _IP, C.POINTER(C.c_double), _IP]),
+    "pt_ctx_room_info": (_I, [_P, _IP, _IP, _FP, _FP]),
     "pt_ctx_counters": (_I, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pt_ctx_stream_info": (_I, [_P] + [C.POINTER(C.c_int32)] * 5),
     "pt_ctx_walk_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_double)]),
@@ -201,7 +202,9 @@ def _preload_torch() -> None:
             pass
 
 
-_OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds"}
+# Entry points an older library may lack when PT_AMD_LIB times it beside this tree (the shipped
+# library has them all; pt_ctx_room_info: the A/B against the build before the room bound).
+_OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info"}
 
 
 def lib() -> C.CDLL:

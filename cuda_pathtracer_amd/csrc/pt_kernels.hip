@@ -87,6 +87,13 @@ struct SceneDev {
     int32_t root_qcode;    // root's code in the quad layout (quad index or leaf code)
     const float* __restrict__ tpack;   // the triangles again as packed 36-byte (v0, e1, e2): k_traverse4's task loads
     const uint32_t* __restrict__ qcull;   // exact t-cull margins of the quads' slots (build_qcull), or null: off
+    // The room (find_room, bound_room): up to six world-box cubes, one per face of the box B they
+    // enclose, bounded as one group by the later bounces.  They are bgeoms[bk[3] .. bk[3] + room_n).
+    int32_t room_n;        // walls of the room (0: no room, nothing below is read)
+    float room_pl[6];      // B, an axis's two planes side by side: (L_a, H_a) at [2a] (-inf / +inf: no wall)
+    float room_out[6];     // the box of the walls' widened world boxes, (lowest wlo_a, highest whi_a) at [2a]
+    uint32_t room_tag[6];  // face 2a (-a), 2a + 1 (+a): the wall's geom index, or +inf's bits (a miss) without one
+    float room_wback;      // the largest DGeom::wback of the walls
 };
 struct CamDev {
     float pos[3], view[3], up[3], right[3], pl[2];
@@ -665,6 +672,64 @@ __device__ __forceinline__ uint32_t tag_bound(float v, uint32_t i) {
     return (b & ~31u) | i;
 }
 
+// The walls of a room (SceneDev::room_*, find_room) bounded as one group: per axis a the two plane
+// parameters tL = (L_a - o_a) * r_a and tH = (H_a - o_a) * r_a in the packed operations of
+// bound_wbox_tagged (L_a: the -a wall's high plane, H_a: the +a wall's low plane, L_a < H_a), then
+//  - the wall AHEAD (+a when r_a's sign bit is clear, else -a) gets the tagged bound
+//    fma(max(tL, tH, 0), rlt, -room_wback), and
+//  - the wall BEHIND is a miss when min(tL, tH) < 0, and otherwise a candidate with bound 0.
+// Three subtractions and three multiplications serve up to six walls, for any origin and direction.
+// The closest hit keeps its bits:
+//  - The bound ahead is one term of bound_wbox_tagged's.  For r_a > 0 the +a wall's slab is (H_a, whi)
+//    with H_a < whi, so its min(tx.x, tx.y) is tx.x = (H_a - o_a) * r_a = tH bit for bit, whatever the
+//    origin, and tH >= tL (H_a > L_a, products round monotonically); likewise tL for r_a < 0.  So
+//    max(tL, tH, 0) <= the wall's E0 (when 0 * inf makes one of them NaN the maxNum chain drops it:
+//    smaller still), and with rlt > 0, room_wback >= the wall's wback and the fma rounding
+//    monotonically the value is a lower bound no larger than the loop's.
+//  - The wall behind is called a miss only where bound_wbox_tagged calls it one: min(tL, tH) < 0 is
+//    that wall's facing plane with a negative parameter, its other plane lies further back, so its
+//    X < 0 there (or -inf for r_a = +-inf).  A zero, NaN or positive parameter (the origin in or beyond
+//    the wall's slab) claims nothing: bound 0.
+//  - The wall ahead is also a miss when the ray is past the walls' common box on another axis b
+//    before it reaches the wall's plane: qa_b < max(tL, tH, 0), qa_b = the larger parameter of the
+//    box's two b-planes (room_out).  Every wall's own widened b-extent lies within those planes, so its
+//    exit parameter on axis b is <= qa_b (same factor r_b, monotone), hence its X <= qa_b < E0:
+//    bound_wbox_tagged's miss.  This is what keeps a ray that leaves through an open face, or past a
+//    neighbouring wall, from being a candidate of every wall ahead (a NaN compares false: no claim).
+//  - A face without a wall has +inf's bits as its tag: ORed in or selected, no candidate.
+//  - Every wall is inserted exactly once per ray: the six faces hold distinct geoms (find_room), each
+//    axis inserts its two faces, one as "ahead" and one as "behind", and the walls are not in the
+//    per-cube loop.  Pass 2 relies on that: the third-smallest bound is never a second entry of one
+//    of the two candidates.
+//  - Pass 2 tests a candidate whenever its bound does not exceed the best exact hit, so weaker valid
+//    bounds and more candidates cannot change the selected hit (minimum t, lowest index on ties).
+// r_a = +-inf (d_a = +-0) needs no case of its own: the signs above are those of the products.
+template <class Ins>
+__device__ __forceinline__ void bound_room_tagged(const SceneDev& S, f3 o, f3 r, float rlt, Ins&& insert_tagged) {
+    float ta[3], qa[3];
+    v2f t[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float oa = at(o, a), ra = at(r, a);
+        t[a] = ((v2f){S.room_pl[2 * a], S.room_pl[2 * a + 1]} - (v2f){oa, oa}) * (v2f){ra, ra};
+        const v2f q = ((v2f){S.room_out[2 * a], S.room_out[2 * a + 1]} - (v2f){oa, oa}) * (v2f){ra, ra};
+        ta[a] = fmaxf(fmaxf(t[a].x, t[a].y), 0.0f);
+        qa[a] = fmaxf(q.x, q.y);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float v = fmaf(ta[a], rlt, -S.room_wback);
+        // the two tags by r_a's sign bit in bit operations (selects between two scalars would first
+        // move both into vector registers): ahead = sign ? wl : wh, behind = the other
+        const uint32_t wl = S.room_tag[2 * a], wh = S.room_tag[2 * a + 1], wx = wl ^ wh;
+        const uint32_t neg = (uint32_t)((int32_t)__float_as_uint(at(r, a)) >> 31);
+        const uint32_t ahead = (neg & wx) ^ wh;
+        const bool past = fminf(qa[(a + 1) % 3], qa[(a + 2) % 3]) < ta[a];
+        insert_tagged(tag_bound(v, 0u) | ahead | (past ? 0x7f800000u : 0u));
+        insert_tagged(fminf(t[a].x, t[a].y) < 0.0f ? 0x7f800000u : (ahead ^ wx));
+    }
+}
+
 // Lower bound on the exact test's world distance for geom g (before the scene's absolute slack),
 // +inf when the exact test surely misses.  Rounding here is irrelevant: only the widened bounds,
 // the relative slack and the comparisons' direction matter (NaNs fall through to "candidate").
@@ -893,7 +958,15 @@ __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsD
         };
         auto insert = [&](float lo, int i) { insert_tagged(lo == kInf ? 0x7f800000u : tag_bound(lo, (uint32_t)i)); };
         const float rlt = rl * S.wb_tslack;
-        for (int j = S.bk[3]; j < S.bk[4]; ++j)   // world-box cubes: packed slabs
+        int j3 = S.bk[3];
+        // the room's walls (the first room_n world-box cubes) as one group (bound_room_tagged).  Later
+        // bounces only: their gmask is all ones, the camera rays keep their masks and the loop.
+        const bool room = SEL && gmask == ~0u && S.room_n > 0;
+        if (room) {
+            bound_room_tagged(S, ro, invd, rlt, insert_tagged);
+            j3 += S.room_n;
+        }
+        for (int j = j3; j < S.bk[4]; ++j)   // world-box cubes: packed slabs
             if ((gmask >> B[j].orig) & 1u) insert_tagged(bound_wbox_tagged(B[j], ro, invd, rlt, (uint32_t)B[j].orig));
         if (SEL) {
             const bool spheres = S.bk[4] < S.bk[5], oboxes = S.bk[1] < S.bk[2];
@@ -933,7 +1006,13 @@ __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsD
                 m1 = c1 ? lo : m1;
                 h1 = c1 ? i : h1;
             };
-            for (int j = S.bk[3]; j < S.bk[4]; ++j)
+            int k3 = S.bk[3];
+            if (room) {   // the room's walls as the pass above takes them
+                auto ins2t = [&](uint32_t t) { ins2(t >= 0x7f800000u ? kInf : __uint_as_float(t), (int)(t & 31u)); };
+                bound_room_tagged(S, r2, invd, rlt, ins2t);
+                k3 += S.room_n;
+            }
+            for (int j = k3; j < S.bk[4]; ++j)
                 if ((gmask >> B[j].orig) & 1u) ins2(bound_geom<3, SEL>(B[j], r2, rd, invd, rl, rinf), B[j].orig);
             for (int j = S.bk[4]; j < S.bk[5]; ++j)
                 if ((gmask >> B[j].orig) & 1u) ins2(bound_geom<4, SEL>(B[j], r2, rd, invd, rl, rinf), B[j].orig);
@@ -969,6 +1048,17 @@ __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsD
             f3 obj = F3(0, 0, 0);
             bool outside;
             const float t = exact_geom(s_geoms[gi], ro, rd, code, obj, outside);
+#if defined(PT_DUP) && PT_DUP == 8   // diagnostic: every exact test again (its cost x the tests per ray)
+            if (SEL) {
+                f3 r2 = ro;
+                asm volatile("" : "+v"(r2.x), "+v"(r2.y), "+v"(r2.z));
+                int code2;
+                f3 obj2 = F3(0, 0, 0);
+                bool out2;
+                const float t2 = exact_geom(s_geoms[gi], r2, rd, code2, obj2, out2);
+                if (__float_as_uint(t2) == 0x7f7ffffeu) atomicAdd(&g_dup_sink, 1u);
+            }
+#endif
             if (t > 0.0f && (t_min > t || (t == t_min && hit_geom >= 0 && gi < hit_geom))) {
                 t_min = t; hit_geom = gi; best_code = code; best_obj = obj; best_outside = outside;
             }
@@ -3398,6 +3488,106 @@ Affine to_affine(const float* m) {   // glm column-major 4x4 -> 3x4 + the exact 
     return a;
 }
 
+// The room of bound_room_tagged: at most one world-box cube (bkind 3) per face -x, +x, -y, +y, -z, +z
+// and the box B between the widened planes with which those walls face each other — H_a the low plane
+// of the +a wall, L_a the high plane of the -a wall, +-inf for a face without a wall.
+//   Per face the candidate is the cube that lies wholly on that side of the centre of the world-box
+// cubes' common box and has the largest cross-section there (a cube serves one face only).  A wall
+// stays only if its extent on the other two axes covers B's, B ending on an open face where the box
+// of the remaining walls ends (their unwidened boxes, which every widened wall of the same extent
+// covers); a wall that does not cover its face would send the rays leaving past it through extra
+// exact tests — slower, never wrong, since bound_room_tagged's bounds hold for any wall.  The room
+// needs three walls (L_a < H_a follows from the selection).  Tags carry five bits, as in the pass
+// itself.  PT_AMD_ROOM=0 leaves the walls in the per-cube loop (A/B and tests; the same bits).
+void find_room(pt_ctx* c) {
+    SceneDev& S = c->args.S;
+    S.room_n = 0;
+    S.room_wback = 0.0f;
+    for (int f = 0; f < 6; ++f) {
+        S.room_pl[f] = (f & 1) ? HUGE_VALF : -HUGE_VALF;
+        S.room_out[f] = (f & 1) ? -HUGE_VALF : HUGE_VALF;
+        S.room_tag[f] = 0x7f800000u;
+    }
+    const std::vector<DGeom>& G = c->hgeoms;
+    const size_t n = G.size();
+    if (n > (size_t)kLdsGeoms) return;
+    if (const char* e = std::getenv("PT_AMD_ROOM"))
+        if (std::atoi(e) == 0) return;
+    // the cubes' own (unwidened) world boxes
+    std::vector<double> elo(3 * n, HUGE_VAL), ehi(3 * n, -HUGE_VAL);
+    double alo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, ahi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    for (size_t i = 0; i < n; ++i) {
+        if (G[i].bkind != 3) continue;
+        for (int corner = 0; corner < 8; ++corner)
+            for (int r = 0; r < 3; ++r) {
+                double v = G[i].xf.c[3][r];
+                for (int k = 0; k < 3; ++k) v += (double)G[i].xf.c[k][r] * ((corner >> k) & 1 ? 0.5 : -0.5);
+                elo[3 * i + r] = std::min(elo[3 * i + r], v);
+                ehi[3 * i + r] = std::max(ehi[3 * i + r], v);
+            }
+        for (int r = 0; r < 3; ++r) {
+            alo[r] = std::min(alo[r], elo[3 * i + r]);
+            ahi[r] = std::max(ahi[r], ehi[3 * i + r]);
+        }
+    }
+    int face[6];
+    std::vector<char> used(n, 0);
+    for (int f = 0; f < 6; ++f) {
+        const int a = f >> 1, b = (a + 1) % 3, e = (a + 2) % 3;
+        const double mid = 0.5 * (alo[a] + ahi[a]);
+        double area = -1.0;
+        face[f] = -1;
+        for (size_t i = 0; i < n; ++i) {
+            if (G[i].bkind != 3 || used[i]) continue;
+            if (!((f & 1) ? (double)G[i].wlo[a] > mid : (double)G[i].whi[a] < mid)) continue;
+            const double ar = ((double)G[i].whi[b] - (double)G[i].wlo[b]) * ((double)G[i].whi[e] - (double)G[i].wlo[e]);
+            if (ar > area) { area = ar; face[f] = (int)i; }
+        }
+        if (face[f] >= 0) used[(size_t)face[f]] = 1;
+    }
+    float pl[6];
+    for (;;) {
+        double blo[3], bhi[3];   // B, ended on its open faces
+        int walls = 0;
+        for (int a = 0; a < 3; ++a) {
+            double wl = HUGE_VAL, wh = -HUGE_VAL;
+            for (int f = 0; f < 6; ++f)
+                if (face[f] >= 0) {
+                    wl = std::min(wl, elo[3 * (size_t)face[f] + a]);
+                    wh = std::max(wh, ehi[3 * (size_t)face[f] + a]);
+                    walls += a == 0;
+                }
+            pl[2 * a] = face[2 * a] >= 0 ? G[(size_t)face[2 * a]].whi[a] : -HUGE_VALF;
+            pl[2 * a + 1] = face[2 * a + 1] >= 0 ? G[(size_t)face[2 * a + 1]].wlo[a] : HUGE_VALF;
+            blo[a] = face[2 * a] >= 0 ? (double)pl[2 * a] : wl;
+            bhi[a] = face[2 * a + 1] >= 0 ? (double)pl[2 * a + 1] : wh;
+        }
+        if (walls < 3) return;
+        bool dropped = false;
+        for (int f = 0; f < 6; ++f) {
+            if (face[f] < 0) continue;
+            const DGeom& d = G[(size_t)face[f]];
+            for (int k = 1; k < 3; ++k) {
+                const int b = ((f >> 1) + k) % 3;
+                if (!((double)d.wlo[b] <= blo[b] && (double)d.whi[b] >= bhi[b])) { face[f] = -1; dropped = true; break; }
+            }
+        }
+        if (!dropped) break;
+    }
+    // (L_a < H_a needs no test: a -a wall's high plane is below the centre, a +a wall's low plane above)
+    for (int f = 0; f < 6; ++f) {
+        S.room_pl[f] = pl[f];
+        if (face[f] < 0) continue;
+        S.room_tag[f] = (uint32_t)face[f];
+        S.room_wback = std::max(S.room_wback, G[(size_t)face[f]].wback);
+        for (int a = 0; a < 3; ++a) {
+            S.room_out[2 * a] = std::min(S.room_out[2 * a], G[(size_t)face[f]].wlo[a]);
+            S.room_out[2 * a + 1] = std::max(S.room_out[2 * a + 1], G[(size_t)face[f]].whi[a]);
+        }
+        ++S.room_n;
+    }
+}
+
 // Widened bounds of the bounded closest-hit pass (bound_geom), sized from R = the largest
 // |coordinate| any ray origin can have: a surface point (+1e-4 offsets) or the camera lens.
 //   qo = inv * ro is computed with <= 4 ulp of S_a = sum_i |inv_ia| R + |inv_3a| absolute error by
@@ -3475,7 +3665,12 @@ void update_bounds(pt_ctx* c, float aperture) {
                     double big = 0.0;
                     for (int k = 0; k < 3; ++k) big = std::max(big, std::fabs(X[r][k]));
                     int n = 0;
-                    for (int k = 0; k < 3; ++k) n += std::fabs(X[r][k]) > 1e-6 * big;
+                    // (1e-4 of the row's axis: a 90-degree rotation in float has cos = -4.4e-8, which next
+                    // to a 0.01 : 10 scale — the Cornell ceiling and back wall — is 4.4e-5 of the thin axis;
+                    // the world box grows by that share of the slab.  Only tightness depends on this bound:
+                    // the world box below holds the widened cube at any rotation, and `back` takes the
+                    // transform's norm.)
+                    for (int k = 0; k < 3; ++k) n += std::fabs(X[r][k]) > 1e-4 * big;
                     aligned = n == 1;
                 }
             }
@@ -3490,8 +3685,15 @@ void update_bounds(pt_ctx* c, float aperture) {
                         hi[r] = std::max(hi[r], v);
                     }
                 }
-                for (int r = 0; r < 3; ++r)
+                // the largest stretch ||X||_2 <= sqrt(||X||_1 ||X||_inf): the largest entry when X has one
+                // entry per row, and still a bound with the small others the test above lets through
+                double n1 = 0.0, ninf = 0.0;
+                for (int r = 0; r < 3; ++r) {
+                    ninf = std::max(ninf, std::fabs(X[r][0]) + std::fabs(X[r][1]) + std::fabs(X[r][2]));
+                    n1 = std::max(n1, std::fabs(X[0][r]) + std::fabs(X[1][r]) + std::fabs(X[2][r]));
                     for (int k = 0; k < 3; ++k) stretch = std::max(stretch, std::fabs(X[r][k]));
+                }
+                stretch = std::max(stretch, std::sqrt(n1 * ninf));
                 const double pad = std::ldexp(R + 1.0, -18);
                 for (int r = 0; r < 3; ++r) {
                     d.wlo[r] = (float)(lo[r] - pad - std::ldexp(std::fabs(lo[r]), -18));
@@ -3534,6 +3736,7 @@ void update_bounds(pt_ctx* c, float aperture) {
     c->args.S.wb_tslack = ts;
     for (DGeom& d : c->hgeoms)
         d.wback = d.bkind == 3 ? std::nextafter((float)((double)d.back * (double)ts), HUGE_VALF) : 0.0f;
+    find_room(c);
 }
 
 // ---- first-bounce geom masks ----------------------------------------------------------------
@@ -4097,14 +4300,27 @@ int build_quads(pt_ctx* c, const std::vector<DNode>& nodes, const std::vector<pt
     return PT_OK;
 }
 
-// SceneDev::bgeoms: the geom table stably ordered by bkind, each row keeping its index in `orig`.
+// SceneDev::bgeoms: the geom table stably ordered by bkind, each row keeping its index in `orig`;
+// among the world-box cubes the walls of the room come first (SceneDev::room_n of them).
 int upload_bound_order(pt_ctx* c) {
     std::vector<DGeom> b;
     int32_t bk[6] = {0, 0, 0, 0, 0, 0};
+    const SceneDev& S = c->args.S;
+    auto wall = [&](size_t i) {   // a wall of the room (find_room)
+        for (int f = 0; f < 6; ++f)
+            if (S.room_n > 0 && S.room_tag[f] == (uint32_t)i) return true;
+        return false;
+    };
     for (int k = 0; k < 5; ++k) {
         bk[k] = (int32_t)b.size();
+        if (k == 3)   // the room's walls first among the world-box cubes
+            for (size_t i = 0; i < c->hgeoms.size(); ++i)
+                if (wall(i)) {
+                    b.push_back(c->hgeoms[i]);
+                    b.back().orig = (int32_t)i;
+                }
         for (size_t i = 0; i < c->hgeoms.size(); ++i)
-            if (c->hgeoms[i].bkind == k) {
+            if (c->hgeoms[i].bkind == k && !(k == 3 && wall(i))) {
                 b.push_back(c->hgeoms[i]);
                 b.back().orig = (int32_t)i;
             }
@@ -4599,6 +4815,18 @@ int pt_ctx_cmask_info(const pt_ctx* c, int32_t* on, double* empty_frac, int32_t*
     if (on) *on = c->args.cmask != nullptr ? 1 : 0;
     if (empty_frac) *empty_frac = c->cmask_empty;
     if (skip_fused) *skip_fused = c->cmask_skip ? 1 : 0;
+    return PT_OK;
+}
+
+int pt_ctx_room_info(const pt_ctx* c, int32_t* walls, int32_t* faces, float* lo, float* hi) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    const SceneDev& S = c->args.S;
+    if (walls) *walls = S.room_n;
+    for (int f = 0; f < 6 && faces; ++f) faces[f] = S.room_n > 0 && S.room_tag[f] < 32u ? (int32_t)S.room_tag[f] : -1;
+    for (int a = 0; a < 3; ++a) {
+        if (lo) lo[a] = S.room_pl[2 * a];
+        if (hi) hi[a] = S.room_pl[2 * a + 1];
+    }
     return PT_OK;
 }
 

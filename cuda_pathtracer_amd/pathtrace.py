@@ -317,6 +317,17 @@ class PathTracer:
         check_pt(lib().pt_ctx_cmask_info(self._h, C.byref(on), C.byref(fr), C.byref(sk)))
         return {"on": bool(on.value), "empty_frac": float(fr.value), "skip_fused": bool(sk.value)}
 
+    def room_info(self) -> dict:
+        """The room whose walls the later bounces bound as one group (pt_ctx_room_info): wall count,
+        the geom index per face (-x, +x, -y, +y, -z, +z; -1: none) and the box between the walls."""
+        if not hasattr(lib(), "pt_ctx_room_info"):
+            raise N.NativeLibraryError("the loaded library (PT_AMD_LIB) predates pt_ctx_room_info")
+        n, faces = C.c_int32(), (C.c_int32 * 6)()
+        lo, hi = (C.c_float * 3)(), (C.c_float * 3)()
+        check_pt(lib().pt_ctx_room_info(self._h, C.byref(n), faces, lo, hi))
+        return {"walls": int(n.value), "faces": [int(v) for v in faces], "lo": [float(v) for v in lo],
+                "hi": [float(v) for v in hi]}
+
     def walk_info(self) -> dict:
         """Mesh scenes: 4-wide walk on/off, its exact t-cull on/off and the share of slots whose
         cull margin can pay (pt_ctx_walk_info)."""

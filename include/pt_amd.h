@@ -247,6 +247,11 @@ int pt_ctx_counters(const pt_ctx* c, uint64_t* mask_builds, uint64_t* flag_syncs
  * the fused first bounce runs its empty-wave instantiation (chosen when that share is >= 0.2;
  * PT_AMD_SKIP_EMPTY=0/1 forces it).  Results are the same bits either way. */
 int pt_ctx_cmask_info(const pt_ctx* c, int32_t* on, double* empty_frac, int32_t* skip_fused);
+/* Inspection: the room whose walls the later bounces bound as one group — the number
+ * of walls (0: no room), the geom index of the wall of each face -x, +x, -y, +y, -z, +z (faces[6], -1
+ * without one) and the box between the walls' facing planes (lo[3], hi[3]; -inf / +inf on a face
+ * without a wall).  Results are the same bits with or without a room (PT_AMD_ROOM=0: never one). */
+int pt_ctx_room_info(const pt_ctx* c, int32_t* walls, int32_t* faces, float* lo, float* hi);
 /* Mesh scenes: whether the BVH walk runs on the 4-wide layout, whether its exact t-cull is on, and
  * the share of the layout's slots whose cull margin can pay.  The cull is on when
  * that share is >= 1/4 (PT_AMD_TCULL=0/1 forces it); it never changes a result. */

@@ -1,6 +1,6 @@
 # Dynamic VALU / SALU cost of each phase of the later-bounce kernel (k_bounce<false,false,0>):
 # variant libraries that run one phase twice on opaque copies of its inputs (-DPT_DUP=1 closest hit,
-# 2 shade, 3 path load); the bench's in-run SQ counters give instructions per segment for each.
+# 2 shade, 3 path load, 4 bounds pass, 8 every exact test); the bench's in-run SQ counters give instructions per segment for each.
 # Build (CPU):  VARIANTS="dup1:-DPT_DUP=1 dup2:-DPT_DUP=2 dup3:-DPT_DUP=3" bash scripts/build_variants.sh
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
