@@ -85,7 +85,19 @@ class DenoiseParams(C.Structure):
         return p
 
 
-assert C.sizeof(DenoiseParams) == 32
+class DenoiseVarParams(C.Structure):
+    """pt_denoise_var_params; DenoiseVarParams.default() = pt_denoise_var_params_default."""
+    _fields_ = [("levels", C.c_int32), ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_p", C.c_float),
+                ("demodulate", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    @classmethod
+    def default(cls) -> "DenoiseVarParams":
+        p = cls()
+        lib().pt_denoise_var_params_default(C.byref(p))
+        return p
+
+
+assert C.sizeof(DenoiseParams) == 32 and C.sizeof(DenoiseVarParams) == 32
 assert C.sizeof(Geom) == 272 and C.sizeof(Material) == 48 and C.sizeof(Triangle) == 124
 assert C.sizeof(BvhNode) == 40
 
@@ -187,6 +199,21 @@ SIGNATURES = {
     "pt_denoiser_run": (_I, [_P, _P, _F, _P, _P, _P, C.POINTER(DenoiseParams), _P, _P]),
     "pt_denoise_host": (_I, [_I, _I, _P, _F, _P, _P, _P, C.POINTER(DenoiseParams), _P]),
     "pt_denoise_image": (_I, [_P, _F, C.POINTER(DenoiseParams), _P]),
+    "pt_moments_create": (_I, [_I, _I, C.POINTER(_P)]),
+    "pt_moments_destroy": (_I, [_P]),
+    "pt_moments_reset": (_I, [_P, _P, _P]),
+    "pt_moments_update": (_I, [_P, _P, _F, _P, _P]),
+    "pt_moments_info": (_I, [_P, _IP, _FP]),
+    "pt_moments_variance": (_I, [_P, _F, _P, _P]),
+    "pt_moments_get": (_I, [_P, _P, _P, _P]),
+    "pt_denoise_var_params_default": (None, [C.POINTER(DenoiseVarParams)]),
+    "pt_denoiser_run_var": (_I, [_P, _P, _F, _P, _P, _P, _P, C.POINTER(DenoiseVarParams), _P, _P, _P]),
+    "pt_denoise_var_host": (_I, [_I, _I, _P, _F, _P, _P, _P, _P, C.POINTER(DenoiseVarParams), _P, _P]),
+    "pt_track_variance": (_I, [_P, _I]),
+    "pt_variance_update": (_I, [_P, _F, _I, _P]),
+    "pt_variance_info": (_I, [_P, _IP, _IP, _FP]),
+    "pt_get_variance": (_I, [_P, _F, _P]),
+    "pt_denoise_image_var": (_I, [_P, _F, C.POINTER(DenoiseVarParams), _P]),
 }
 
 _lib = None
@@ -203,8 +230,12 @@ def _preload_torch() -> None:
 
 
 # Entry points an older library may lack when PT_AMD_LIB times it beside this tree (the shipped
-# library has them all; pt_ctx_room_info: the A/B against the build before the room bound).
-_OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info"}
+# library has them all; pt_ctx_room_info: the A/B against the build before the room bound; the
+# variance entry points: the A/B against the build before them).
+_OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_moments_create",
+             "pt_moments_destroy", "pt_moments_reset", "pt_moments_update", "pt_moments_info", "pt_moments_variance",
+             "pt_moments_get", "pt_denoise_var_params_default", "pt_denoiser_run_var", "pt_denoise_var_host",
+             "pt_track_variance", "pt_variance_update", "pt_variance_info", "pt_get_variance", "pt_denoise_image_var"}
 
 
 def lib() -> C.CDLL:

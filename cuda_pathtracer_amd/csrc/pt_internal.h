@@ -54,5 +54,9 @@ int decode_jpeg(const uint8_t* data, size_t size, int32_t* width, int32_t* heigh
 int load_texture_file(TextureHost& t);
 // Denoiser (pt_denoise.hip): the argument checks of pt_denoiser_run that need no device
 int denoise_check(const pt_denoise_params* p, float samples);
+int denoise_var_check(const pt_denoise_var_params* p, float samples);
+// pt_moments: the argument checks of pt_moments_update / pt_moments_variance that need no device
+int moments_update_check(const pt_moments* m, float batch_samples);
+int moments_variance_check(const pt_moments* m, float samples);
 
 }  // namespace pt

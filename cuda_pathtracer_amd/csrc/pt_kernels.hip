@@ -3391,8 +3391,16 @@ struct pt_ctx {
     pt_flags ahead_flags{};
     uint8_t* colflag = nullptr;   // 2 x P flag bytes (KArgs::colflag), pass halves like colbuf; zero between passes
     uint8_t* ahead_flag = nullptr;   // npix flag bytes of the render-ahead colours
+    // Variance tracking (pt_track_variance, world == 1): luminance moments of the accumulator's batch
+    // means, and the first-hit planes gA | gB | alb (12 floats per pixel) whose albedo demodulates them.
+    // The planes are filled at the first update after tracking starts or the accumulator is rebased.
+    pt_moments* mom = nullptr;
+    float* mom_g = nullptr;
+    bool mom_g_valid = false;
 
     ~pt_ctx() {
+        if (mom) (void)pt_moments_destroy(mom);
+        if (mom_g) (void)hipFree(mom_g);
         g_busy_streams.fetch_sub(busy_streams);
         for (auto& e : events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         for (int h = 0; h < 2; ++h) {
@@ -5128,6 +5136,13 @@ static int wait_finalize(pt_ctx* c, hipStream_t st) {
     return PT_OK;
 }
 
+// A tracking context (pt_track_variance) whose accumulator was just replaced on `st`: the moments
+// start again from it.
+static int rebase_variance(pt_ctx* c, hipStream_t st) {
+    c->mom_g_valid = false;
+    return pt_moments_reset(c->mom, c->args.image, st);
+}
+
 int pt_preview_rgba(pt_ctx* c, int32_t iter, uint8_t* d_rgba, void* stream) {
     if (!c || !d_rgba || iter <= 0) return pt::fail(PT_ERR_ARG, "bad argument");
     const int npix = c->args.tile.npix;
@@ -5207,6 +5222,10 @@ int pt_set_accum(pt_ctx* c, const float* host_rgb) {
     for (float& v : img)
         if (v == 0.0f) v = 0.0f;   // (-0 == 0: both zeros become +0)
     HIP_TRY(io_copy(c, c->args.image, img.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    if (c->mom) {
+        if (int rc = rebase_variance(c, c->io_stream)) return rc;
+        return mark_ctx(c, c->io_stream);
+    }
     return PT_OK;
 }
 
@@ -5289,7 +5308,118 @@ int pt_reset_image(pt_ctx* c, void* stream) {
     if (!c) return pt::fail(PT_ERR_ARG, "null context");
     if (int rc = wait_finalize(c, (hipStream_t)stream)) return rc;
     HIP_TRY(hipMemsetAsync(c->args.image, 0, (size_t)c->args.tile.npix * 3 * sizeof(float), (hipStream_t)stream));
+    if (c->mom)
+        if (int rc = rebase_variance(c, (hipStream_t)stream)) return rc;
     return mark_ctx(c, (hipStream_t)stream);
+}
+
+// ---- variance tracking ---------------------------------------------------------
+int pt_track_variance(pt_ctx* c, int32_t on) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    if (c->args.tile.world > 1) return pt::fail(PT_ERR_ARG, "variance tracking needs the whole image (world == 1)");
+    if (int rc = wait_ctx(c)) return rc;
+    if (!on) {
+        if (c->mom) (void)pt_moments_destroy(c->mom);
+        if (c->mom_g) (void)hipFree(c->mom_g);
+        c->mom = nullptr;
+        c->mom_g = nullptr;
+        c->mom_g_valid = false;
+        return PT_OK;
+    }
+    if (c->mom) return PT_OK;
+    const int W = c->args.tile.W;
+    const size_t npix = (size_t)c->args.tile.npix;
+    if (int rc = pt_moments_create(W, (int32_t)(npix / W), &c->mom)) return rc;
+    if (hipMalloc((void**)&c->mom_g, npix * 12 * sizeof(float)) != hipSuccess) {
+        (void)pt_moments_destroy(c->mom);
+        c->mom = nullptr;
+        return pt::fail(PT_ERR_NOMEM, "hipMalloc (variance tracking)");
+    }
+    if (int rc = rebase_variance(c, c->io_stream)) return rc;
+    return mark_ctx(c, c->io_stream);
+}
+
+// The context's first-hit planes for variance tracking, on st (pt_gbuffer orders and marks itself).
+static int variance_planes(pt_ctx* c, hipStream_t st) {
+    const size_t npix = (size_t)c->args.tile.npix;
+    if (int rc = pt_gbuffer(c, c->mom_g, c->mom_g + 4 * npix, c->mom_g + 8 * npix, nullptr, st)) return rc;
+    c->mom_g_valid = true;
+    return PT_OK;
+}
+
+int pt_variance_update(pt_ctx* c, float batch_samples, int32_t demodulate, void* stream) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    if (!c->mom) return pt::fail(PT_ERR_ARG, "variance tracking is off (pt_track_variance)");
+    if (int rc = pt::moments_update_check(c->mom, batch_samples)) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = wait_finalize(c, st)) return rc;
+    if (demodulate && !c->mom_g_valid)
+        if (int rc = variance_planes(c, st)) return rc;
+    const float* alb = demodulate ? c->mom_g + 8 * (size_t)c->args.tile.npix : nullptr;
+    if (int rc = pt_moments_update(c->mom, c->args.image, batch_samples, alb, st)) return rc;
+    return mark_ctx(c, st);
+}
+
+int pt_variance_info(const pt_ctx* c, int32_t* on, int32_t* batches, float* batch_samples) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    if (on) *on = c->mom ? 1 : 0;
+    if (batches) *batches = 0;
+    if (batch_samples) *batch_samples = 0.0f;
+    return c->mom ? pt_moments_info(c->mom, batches, batch_samples) : PT_OK;
+}
+
+int pt_get_variance(pt_ctx* c, float samples, float* host_var) {
+    if (!c || !host_var) return pt::fail(PT_ERR_ARG, "null argument");
+    if (!c->mom) return pt::fail(PT_ERR_ARG, "variance tracking is off (pt_track_variance)");
+    if (int rc = pt::moments_variance_check(c->mom, samples)) return rc;
+    const size_t npix = (size_t)c->args.tile.npix;
+    float* d = nullptr;
+    if (hipMalloc((void**)&d, npix * sizeof(float)) != hipSuccess) return pt::fail(PT_ERR_NOMEM, "hipMalloc (variance)");
+    int rc = wait_finalize(c, c->io_stream);
+    if (!rc) rc = pt_moments_variance(c->mom, samples, d, c->io_stream);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        rc = mark_ctx(c, c->io_stream);
+        e = hipMemcpyAsync(host_var, d, npix * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(c->io_stream);
+    if (e == hipSuccess) e = e2;
+    (void)hipFree(d);
+    if (rc) return rc;
+    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_get_variance: ") + hipGetErrorString(e));
+    return PT_OK;
+}
+
+// Like pt_denoise_image, with the tracked variance: fresh first-hit planes (into the context's own),
+// the variance of `samples` samples, the filter and the copy, all on the io stream.
+int pt_denoise_image_var(pt_ctx* c, float samples, const pt_denoise_var_params* prm, float* host_out_rgb) {
+    if (!c || !host_out_rgb) return pt::fail(PT_ERR_ARG, "null argument");
+    if (c->args.tile.world > 1) return pt::fail(PT_ERR_ARG, "pt_denoise_image_var needs the whole image (world == 1)");
+    if (!c->mom) return pt::fail(PT_ERR_ARG, "variance tracking is off (pt_track_variance)");
+    if (int rc = pt::denoise_var_check(prm, samples)) return rc;
+    if (int rc = pt::moments_variance_check(c->mom, samples)) return rc;
+    const int W = c->args.tile.W;
+    const size_t npix = (size_t)c->args.tile.npix;
+    float* d = nullptr;   // var | out
+    if (hipMalloc((void**)&d, npix * 4 * sizeof(float)) != hipSuccess) return pt::fail(PT_ERR_NOMEM, "hipMalloc (denoise)");
+    pt_denoiser* dn = nullptr;
+    int rc = pt_denoiser_create(W, (int32_t)(npix / W), &dn);
+    if (!rc) rc = variance_planes(c, c->io_stream);
+    if (!rc) rc = pt_moments_variance(c->mom, samples, d, c->io_stream);
+    if (!rc) rc = pt_denoiser_run_var(dn, c->args.image, samples, d, c->mom_g, c->mom_g + 4 * npix, c->mom_g + 8 * npix, prm,
+                                      d + npix, nullptr, c->io_stream);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        rc = mark_ctx(c, c->io_stream);
+        e = hipMemcpyAsync(host_out_rgb, d + npix, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(c->io_stream);
+    if (e == hipSuccess) e = e2;
+    pt_denoiser_destroy(dn);
+    (void)hipFree(d);
+    if (rc) return rc;
+    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_denoise_image_var: ") + hipGetErrorString(e));
+    return PT_OK;
 }
 
 int pt_stats(pt_ctx* c, pt_stats_t* out) {

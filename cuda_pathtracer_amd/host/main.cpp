@@ -3,10 +3,14 @@
 // window — pathtraceInit, `iterations` calls of pathtrace(), saveImage() (main.cpp:88-112) and
 // pathtraceFree().  The camera is the first-frame orbit recompute (done by pt_scene_finalize).
 //
-//   pathtracer_amd SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise] [--aov DIR]
+//   pathtracer_amd SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise]
+//                  [--denoise-variance] [--aov DIR]
 // --denoise also writes the a-trous-filtered image (pt_denoise_image) as ...samp.denoised.png (and
-// .denoised.hdr with --hdr); --aov DIR writes the first-hit G-buffer planes (pt_get_gbuffer) as raw
-// little-endian float32 files with a one-line JSON sidecar of their shapes.
+// .denoised.hdr with --hdr); --denoise-variance tracks the per-pixel variance (pt_track_variance, one
+// pt_variance_update per iteration; the raw image is the same) and writes the variance-guided filter's
+// image (pt_denoise_image_var; the plain filter's with fewer than 2 iterations) as
+// ...samp.denoised-var.png (and .hdr with --hdr); --aov DIR writes the first-hit G-buffer planes
+// (pt_get_gbuffer) as raw little-endian float32 files with a one-line JSON sidecar of their shapes.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -29,15 +33,15 @@ std::string currentTimeString() {   // preview.cpp:21-28
 }
 
 // saveImage (main.cpp:88-112): divide by the sample count, mirror x, clamp, x255, PNG.
-// `denoised`: a per-sample image to write instead (as ...samp.denoised.png / .hdr).
+// `denoised`: a per-sample image to write instead (as ...samp.<tag>.png / .hdr).
 std::string saveImage(const Scene& scene, const std::string& dir, const std::string& start, int iteration,
-                      bool hdr = false, const float* denoised = nullptr) {
+                      bool hdr = false, const float* denoised = nullptr, const char* tag = "denoised") {
     const float samples = (float)iteration;
     std::ostringstream ss;
     ss << scene.state.imageName << "." << start << "." << samples << "samp";
     std::string filename = ss.str();
     if (!dir.empty()) filename = dir + "/" + filename;
-    if (denoised) filename += ".denoised";
+    if (denoised) filename += std::string(".") + tag;
     filename += hdr ? ".hdr" : ".png";   // Image::savePNG / saveHDR append the extension (image.cpp:22-49)
     const int W = scene.state.camera.res[0], H = scene.state.camera.res[1];
     const float* rgb = denoised ? denoised : reinterpret_cast<const float*>(scene.state.image.data());
@@ -93,13 +97,13 @@ int main(int argc, char** argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2) {
         std::printf("Usage: %s SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise] "
-                    "[--aov DIR]\n", argv[0]);
+                    "[--denoise-variance] [--aov DIR]\n", argv[0]);
         return 1;
     }
     const char* sceneFile = argv[1];
     int iterations = -1;
     std::string out_dir, aov_dir;
-    bool sort = false, png = true, hdr = false, denoise = false, aov = false;
+    bool sort = false, png = true, hdr = false, denoise = false, denoise_var = false, aov = false;
     for (int i = 2; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--iterations") && i + 1 < argc) iterations = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out_dir = argv[++i];
@@ -107,6 +111,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--no-png")) png = false;
         else if (!std::strcmp(argv[i], "--hdr")) hdr = true;   // also write the saveHDR .hdr file
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
+        else if (!std::strcmp(argv[i], "--denoise-variance")) denoise_var = true;
         else if (!std::strcmp(argv[i], "--aov") && i + 1 < argc) { aov_dir = argv[++i]; aov = true; }
         else {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
@@ -121,11 +126,19 @@ int main(int argc, char** argv) {
     const int total = iterations > 0 ? iterations : (int)scene->state.iterations;
 
     pathtraceInit(scene);
+    if (denoise_var && pt_track_variance(pathtraceContext(), 1)) {
+        std::fprintf(stderr, "error: variance tracking: %s\n", pt_last_error());
+        return EXIT_FAILURE;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     int iteration = 0;
     while (iteration < total) {
         ++iteration;
         pathtrace(nullptr, 0, iteration);
+        if (denoise_var && pt_variance_update(pathtraceContext(), 1.0f, 1, nullptr)) {
+            std::fprintf(stderr, "error: variance update: %s\n", pt_last_error());
+            return EXIT_FAILURE;
+        }
     }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     pt_stats_t st{};
@@ -144,6 +157,28 @@ int main(int argc, char** argv) {
         }
         std::printf("wrote %s\n", saveImage(*scene, out_dir, startTimeString, iteration, false, dn.data()).c_str());
         if (hdr) std::printf("wrote %s\n", saveImage(*scene, out_dir, startTimeString, iteration, true, dn.data()).c_str());
+    }
+    if (denoise_var) {
+        std::vector<float> dn((size_t)scene->state.camera.res[0] * scene->state.camera.res[1] * 3);
+        int rc;
+        if (iteration >= 2) {
+            pt_denoise_var_params prm;
+            pt_denoise_var_params_default(&prm);
+            rc = pt_denoise_image_var(pathtraceContext(), (float)iteration, &prm, dn.data());
+        } else {   // one batch gives no variance: the plain filter
+            pt_denoise_params prm;
+            pt_denoise_params_default(&prm);
+            rc = pt_denoise_image(pathtraceContext(), (float)iteration, &prm, dn.data());
+        }
+        if (rc) {
+            std::fprintf(stderr, "error: denoise: %s\n", pt_last_error());
+            return EXIT_FAILURE;
+        }
+        std::printf("wrote %s\n",
+                    saveImage(*scene, out_dir, startTimeString, iteration, false, dn.data(), "denoised-var").c_str());
+        if (hdr)
+            std::printf("wrote %s\n",
+                        saveImage(*scene, out_dir, startTimeString, iteration, true, dn.data(), "denoised-var").c_str());
     }
     if (aov) saveAovs(*scene, aov_dir);
     pathtraceFree();

@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._native import DenoiseParams, check_pt, lib  # noqa: F401
+from ._native import DenoiseParams, DenoiseVarParams, check_pt, lib  # noqa: F401
 
 SPHERE, CUBE, MESH = 0, 1, 2
 
@@ -400,6 +400,38 @@ class PathTracer:
         check_pt(lib().pt_denoise_image(self._h, float(samples), C.byref(prm), out.ctypes.data))
         return out
 
+    def track_variance(self, on: bool = True) -> None:
+        """Start (from the accumulator as it stands) or stop tracking the per-pixel variance of the
+        luminance (pt_track_variance; world == 1 only).  Passes are not changed: call variance_update
+        after each."""
+        check_pt(lib().pt_track_variance(self._h, int(bool(on))))
+
+    def variance_update(self, batch_samples: float | None = None, demodulate: bool = True, stream=None) -> None:
+        """One batch: what the accumulator gained since the last update, batch_samples samples (default:
+        the context's spp), divided by the first-hit albedo with `demodulate` (pt_variance_update)."""
+        bs = float(self.spp if batch_samples is None else batch_samples)
+        check_pt(lib().pt_variance_update(self._h, bs, int(bool(demodulate)), _stream_ptr(stream)))
+
+    def variance_info(self) -> dict:
+        on, n, bs = C.c_int32(), C.c_int32(), C.c_float()
+        check_pt(lib().pt_variance_info(self._h, C.byref(on), C.byref(n), C.byref(bs)))
+        return {"on": bool(on.value), "batches": int(n.value), "batch_samples": float(bs.value)}
+
+    def variance(self, samples: float) -> np.ndarray:
+        """(rows, W) float32: the variance of the luminance of the accumulator's per-sample mean over
+        `samples` samples, from the tracked batch means (pt_get_variance; needs 2 batches)."""
+        out = np.empty((self.rows, self.width), np.float32)
+        check_pt(lib().pt_get_variance(self._h, float(samples), out.ctypes.data))
+        return out
+
+    def denoised_variance(self, samples: float, params: "N.DenoiseVarParams | None" = None) -> np.ndarray:
+        """denoised() with the variance-guided filter and the tracked variance (pt_denoise_image_var;
+        tracking on and at least 2 batches, else PtError).  The accumulator is not modified."""
+        prm = params if params is not None else N.DenoiseVarParams.default()
+        out = np.empty((self.rows, self.width, 3), np.float32)
+        check_pt(lib().pt_denoise_image_var(self._h, float(samples), C.byref(prm), out.ctypes.data))
+        return out
+
     def stats(self) -> dict:
         s = N.Stats()
         check_pt(lib().pt_stats(self._h, C.byref(s)))
@@ -450,6 +482,27 @@ def denoise(image: np.ndarray, samples: float, gbuffer: dict, params: "N.Denoise
     return out
 
 
+def denoise_variance(image: np.ndarray, samples: float, variance: np.ndarray, gbuffer: dict,
+                     params: "N.DenoiseVarParams | None" = None, return_variance: bool = False):
+    """pt_denoise_var_host: denoise() with the variance-guided filter; `variance` is the (H, W) variance of
+    the luminance of image / samples (demodulated when params.demodulate), as PathTracer.variance gives it.
+    With return_variance also the (H, W) variance of the filtered image."""
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    shape = img.shape[:2]
+    var = np.ascontiguousarray(variance, dtype=np.float32).reshape(shape)
+    mat = np.ascontiguousarray(gbuffer["mat"], dtype=np.int32).view(np.float32)
+    ga = _plane4(gbuffer["normal"], mat, shape)
+    gb = _plane4(gbuffer["position"], np.asarray(gbuffer["t"], np.float32), shape)
+    al = _plane4(gbuffer["albedo"], np.zeros(shape, np.float32), shape)
+    prm = params if params is not None else N.DenoiseVarParams.default()
+    out = np.empty(shape + (3,), np.float32)
+    ovar = np.empty(shape, np.float32) if return_variance else None
+    check_pt(lib().pt_denoise_var_host(shape[1], shape[0], img.ctypes.data, float(samples), var.ctypes.data,
+                                       ga.ctypes.data, gb.ctypes.data, al.ctypes.data, C.byref(prm), out.ctypes.data,
+                                       ovar.ctypes.data if return_variance else None))
+    return (out, ovar) if return_variance else out
+
+
 def tonemap(image: np.ndarray, samples: float) -> np.ndarray:
     """saveImage + Image::savePNG pixel math (x-mirrored, clamp, x255, truncation) -> (H, W, 3) uint8."""
     img = np.ascontiguousarray(image, dtype=np.float32)
@@ -483,22 +536,34 @@ def save_image_hdr(path: str, image: np.ndarray, samples: float) -> str:
 
 
 def render(scene_path: str, iterations: int | None = None, out_dir: str | None = None,
-           gui: GuiDataContainer | None = None, denoise: bool = False) -> tuple[np.ndarray, str | None]:
+           gui: GuiDataContainer | None = None, denoise: "bool | str" = False) -> tuple[np.ndarray, str | None]:
     """Headless runCuda loop (main.cpp:114-168): ITERATIONS passes, then saveImage.  denoise=True
-    additionally saves FILE.<UTC>.<spp>samp.denoised.png (PathTracer.denoised); the raw PNG is the same."""
+    additionally saves FILE.<UTC>.<spp>samp.denoised.png (PathTracer.denoised); the raw PNG is the same.
+    denoise="variance" tracks the variance (an update after every pass; the passes and the raw PNG are
+    the same) and saves FILE.<UTC>.<spp>samp.denoised-var.png (PathTracer.denoised_variance, or the
+    plain filter when there are fewer than 2 batches)."""
+    if denoise not in (False, True, "variance"):
+        raise ValueError(f"denoise must be False, True or 'variance', not {denoise!r}")
     scene = Scene(scene_path)
     st = scene.state()
     iters = iterations if iterations is not None else st.iterations
     pt = PathTracer(scene, gui)
+    if denoise == "variance":
+        pt.track_variance(True)
     for it in range(1, iters + 1):
         pt.render_pass(it)
+        if denoise == "variance":
+            pt.variance_update()
     img = pt.image()
     path = None
     if out_dir is not None:
         stamp = time.strftime("%Y-%m-%d_%H-%M-%Sz", time.gmtime())
         path = str(Path(out_dir) / f"{st.imageName}.{stamp}.{iters}samp.png")
         save_image(path, img, iters)
-        if denoise:
+        if denoise == "variance":
+            dn = pt.denoised_variance(iters) if pt.variance_info()["batches"] >= 2 else pt.denoised(iters)
+            save_image(path[:-len(".png")] + ".denoised-var.png", dn, 1.0)
+        elif denoise:
             save_image(path[:-len(".png")] + ".denoised.png", pt.denoised(iters), 1.0)
     pt.free()
     return img, path

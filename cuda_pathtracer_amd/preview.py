@@ -91,6 +91,10 @@ class PreviewSession:
         self._read = read_preview or self._device_preview
         self._dbuf = None
         self.denoise = False         # panel: show the a-trous-filtered image (PathTracer.denoised)
+        # panel: show the variance-guided filter's image (PathTracer.denoised_variance); the context
+        # tracks the variance while it is on (_tracking: the current context has been told to)
+        self.denoise_variance = False
+        self._tracking = False
         self.lock = threading.RLock()
 
     # ---- callbacks (main.cpp:189-271) --------------------------------------------------------
@@ -149,6 +153,8 @@ class PreviewSession:
         with self.lock:
             if name == "denoise":   # display only: the accumulation, saving and S are untouched
                 self.denoise = bool(value)
+            elif name == "denoise_variance":   # display only too; tracking starts at the next iteration
+                self.denoise_variance = bool(value)
             elif name in GENERAL_SETTINGS or name in ("SSAA", "DoF"):
                 setattr(self.gui, name, bool(value))
             elif name in SLIDERS:
@@ -173,12 +179,21 @@ class PreviewSession:
             if self.iteration == 0:   # pathtraceFree + pathtraceInit
                 self._free()
                 self.ctx = self._factory(self.scene, self.gui)
+                self._tracking = False
             if self.iteration < self.iterations:
+                if self.denoise_variance != self._tracking:   # from the accumulator as it stands: no restart
+                    self.ctx.track_variance(self.denoise_variance)
+                    self._tracking = self.denoise_variance
                 self.iteration += 1
                 # pathtrace(pbo, frame, iteration): InitDataContainer's flags, one iteration, the PBO
                 self.ctx.set_flags(self.gui)
                 self.ctx.render_pass(self.iteration)
-                self.rgba = self._denoised_preview() if self.denoise else self._read(self.ctx, self.iteration)
+                if self._tracking:
+                    self.ctx.variance_update()
+                if self.denoise or self.denoise_variance:
+                    self.rgba = self._denoised_preview()
+                else:
+                    self.rgba = self._read(self.ctx, self.iteration)
             else:
                 self.save_image()
                 self._free()
@@ -196,8 +211,13 @@ class PreviewSession:
 
     def _denoised_preview(self) -> np.ndarray:
         """The PBO contents of the denoised image: the tonemapped bytes, un-mirrored back into the
-        PBO's pixel order (display_rgb mirrors x), alpha 0 as sendImageToPBO leaves it."""
-        rgb = tonemap(self.ctx.denoised(float(self.iteration)), 1.0)[:, ::-1]
+        PBO's pixel order (display_rgb mirrors x), alpha 0 as sendImageToPBO leaves it.  The
+        variance-guided image once two batches exist, the plain filter's before that."""
+        if self.denoise_variance and self._tracking and self.ctx.variance_info()["batches"] >= 2:
+            img = self.ctx.denoised_variance(float(self.iteration))
+        else:
+            img = self.ctx.denoised(float(self.iteration))
+        rgb = tonemap(img, 1.0)[:, ::-1]
         out = np.zeros((self.height, self.width, 4), np.uint8)
         out[..., :3] = rgb
         return out
@@ -243,7 +263,7 @@ class PreviewSession:
                 "traced_depth": self.traced_depth,   # "Traced Depth %d"
                 "ms_per_frame": ft * 1e3, "fps": (1.0 / ft) if ft > 0 else 0.0,
                 "settings": {**{k: getattr(self.gui, k) for k in GENERAL_SETTINGS + VISUAL_SETTINGS},
-                             "denoise": self.denoise},
+                             "denoise": self.denoise, "denoise_variance": self.denoise_variance},
                 "camera": {"phi": float(self.phi), "theta": float(self.theta), "zoom": float(self.zoom),
                            "look_at": [float(v) for v in self.look_at],
                            "position": [float(v) for v in cam.position[:3]]},
@@ -288,7 +308,8 @@ fieldset{border:1px solid #555;margin:0 0 8px 0} input[type=range]{width:160px}<
 <label><input type="checkbox" id="russianRoulette"> Russian roulette</label><br>
 <label><input type="checkbox" id="sortbyMaterial"> Sort by material (can harm performance)</label><br>
 <label><input type="checkbox" id="useThrustPartition"> Use thrust library for path termination</label><br>
-<label><input type="checkbox" id="denoise"> Show the denoised image (edge-avoiding a-trous filter)</label></fieldset>
+<label><input type="checkbox" id="denoise"> Show the denoised image (edge-avoiding a-trous filter)</label><br>
+<label><input type="checkbox" id="denoise_variance"> Show the variance-guided denoised image (tracks per-pixel variance)</label></fieldset>
 <fieldset><legend>Visual settings</legend>
 <label><input type="checkbox" id="SSAA"> Enable stochastic sampled antialiasing</label><br>
 <label><input type="checkbox" id="DoF"> Enable DoF effects</label><br>
@@ -307,7 +328,7 @@ img.addEventListener('mousemove',e=>{const p=pos(e);post({kind:'move',x:p.x,y:p.
 img.addEventListener('contextmenu',e=>e.preventDefault());
 window.addEventListener('keydown',e=>{const k=e.key==='Escape'?'ESCAPE':e.key===' '?'SPACE':e.key.toUpperCase();
  if(['ESCAPE','SPACE','S'].includes(k)){e.preventDefault();post({kind:'key',key:k});}});
-for(const id of ['russianRoulette','sortbyMaterial','useThrustPartition','denoise','SSAA','DoF'])
+for(const id of ['russianRoulette','sortbyMaterial','useThrustPartition','denoise','denoise_variance','SSAA','DoF'])
  document.getElementById(id).addEventListener('change',e=>post({kind:'setting',name:id,value:e.target.checked}));
 for(const id of ['aperture','focal_len'])
  document.getElementById(id).addEventListener('input',e=>post({kind:'setting',name:id,value:parseFloat(e.target.value)}));

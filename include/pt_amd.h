@@ -412,6 +412,61 @@ int pt_denoise_host(int32_t width, int32_t height, const float* rgb, float sampl
  * PT_ERR_ARG when world > 1.  The accumulator is not modified.  Synchronous. */
 int pt_denoise_image(pt_ctx* c, float samples, const pt_denoise_params* p, float* host_out_rgb);
 
+/* ---- per-pixel variance and the variance-guided filter -------------------- */
+/* Luminance moments of batch means.  The object owns a copy of the accumulator as last seen (prev)
+ * and the sums m1, m2 of lum(d) and lum(d)^2 over the updates, d = (rgb - prev) / batch_samples per
+ * component (divided by alb where alb.k >= 2^-10 when d_alb is given: npix float4, as pt_gbuffer
+ * writes it), lum(c) = (0.2126 c.x + 0.7152 c.y) + 0.0722 c.z.  Device pointers, asynchronous on
+ * `stream` (the caller orders the calls of one object), no context needed.
+ *   reset:    m1 = m2 = 0, batches = 0, prev = d_base_rgb (zeros when NULL)
+ *   update:   one batch; batch_samples finite, > 0 and the same as the first update's since the last
+ *             reset, else PT_ERR_ARG before any device call
+ *   variance: d_var[npix] = max(0, m2/n - (m1/n)^2) * (n * batch_samples) / ((n - 1) * samples): the
+ *             variance of the luminance of the per-sample mean of `samples` samples; needs n >= 2
+ *             batches and samples > 0 (PT_ERR_ARG)
+ *   get:      synchronous, host arrays (npix, npix, npix * 3), any may be NULL (for tests) */
+typedef struct pt_moments pt_moments;
+int pt_moments_create(int32_t width, int32_t height, pt_moments** out);
+int pt_moments_destroy(pt_moments* m);
+int pt_moments_reset(pt_moments* m, const float* d_base_rgb, void* stream);
+int pt_moments_update(pt_moments* m, const float* d_rgb, float batch_samples, const float* d_alb, void* stream);
+int pt_moments_info(const pt_moments* m, int32_t* batches, float* batch_samples);
+int pt_moments_variance(pt_moments* m, float samples, float* d_var, void* stream);
+int pt_moments_get(pt_moments* m, float* h_m1, float* h_m2, float* h_prev_rgb);
+
+/* The a-trous filter of pt_denoiser_run with the colour term driven by a per-pixel variance of the
+ * luminance (which it filters along with the colour) instead of a fixed sigma_c: the exact fp32
+ * definition is DESIGN.md §11.  sigma_l scales the standard deviation and is the same at every level. */
+typedef struct pt_denoise_var_params {
+    int32_t levels;               /* default 5 */
+    float sigma_l, sigma_n, sigma_p; /* luminance (in standard deviations), normal, plane distance; defaults 1, 0.3, 0.2 */
+    int32_t demodulate;           /* default 1 */
+    int32_t reserved[3];
+} pt_denoise_var_params;
+void pt_denoise_var_params_default(pt_denoise_var_params* p);
+/* Like pt_denoiser_run.  d_var: W*H floats, the variance of lum(rgb / samples [/ alb]); d_out_var
+ * (may be NULL): the filtered image's variance.  Outputs must not alias inputs. */
+int pt_denoiser_run_var(pt_denoiser* d, const float* d_rgb, float samples, const float* d_var, const float* d_gA,
+                        const float* d_gB, const float* d_alb, const pt_denoise_var_params* p, float* d_out_rgb,
+                        float* d_out_var, void* stream);
+int pt_denoise_var_host(int32_t width, int32_t height, const float* rgb, float samples, const float* var,
+                        const float* gA, const float* gB, const float* alb, const pt_denoise_var_params* p,
+                        float* out_rgb, float* out_var);
+/* Variance tracking of a world == 1 context (PT_ERR_ARG otherwise): a pt_moments over its accumulator.
+ * pt_track_variance(c, 1) starts from the accumulator as it stands (a no-op when already tracking);
+ * (c, 0) frees everything.  pt_variance_update is called after a pass of batch_samples samples (the
+ * context's spp); it orders itself like pt_copy_image and, with `demodulate`, divides the batch means
+ * by the context's first-hit albedo (computed at the first update after tracking starts or the
+ * accumulator is rebased).  pt_render_pass does nothing for tracking.  pt_reset_image and pt_set_accum
+ * rebase a tracking context: sums and count to zero, prev = the new accumulator.
+ * pt_get_variance: pt_moments_variance into a host array (npix floats; synchronous).
+ * pt_denoise_image_var: like pt_denoise_image with the tracked variance (needs >= 2 batches). */
+int pt_track_variance(pt_ctx* c, int32_t on);
+int pt_variance_update(pt_ctx* c, float batch_samples, int32_t demodulate, void* stream);
+int pt_variance_info(const pt_ctx* c, int32_t* on, int32_t* batches, float* batch_samples);
+int pt_get_variance(pt_ctx* c, float samples, float* host_var);
+int pt_denoise_image_var(pt_ctx* c, float samples, const pt_denoise_var_params* p, float* host_out_rgb);
+
 #ifdef __cplusplus
 }
 #endif
