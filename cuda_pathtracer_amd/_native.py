@@ -97,7 +97,19 @@ class DenoiseVarParams(C.Structure):
         return p
 
 
-assert C.sizeof(DenoiseParams) == 32 and C.sizeof(DenoiseVarParams) == 32
+class TemporalParams(C.Structure):
+    """pt_temporal_params; TemporalParams.default() = pt_temporal_params_default."""
+    _fields_ = [("max_history", C.c_float), ("min_ndot", C.c_float), ("plane_tol", C.c_float),
+                ("demodulate", C.c_int32), ("min_frames", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    @classmethod
+    def default(cls) -> "TemporalParams":
+        p = cls()
+        lib().pt_temporal_params_default(C.byref(p))
+        return p
+
+
+assert C.sizeof(DenoiseParams) == 32 and C.sizeof(DenoiseVarParams) == 32 and C.sizeof(TemporalParams) == 32
 assert C.sizeof(Geom) == 272 and C.sizeof(Material) == 48 and C.sizeof(Triangle) == 124
 assert C.sizeof(BvhNode) == 40
 
@@ -214,6 +226,17 @@ SIGNATURES = {
     "pt_variance_info": (_I, [_P, _IP, _IP, _FP]),
     "pt_get_variance": (_I, [_P, _F, _P]),
     "pt_denoise_image_var": (_I, [_P, _F, C.POINTER(DenoiseVarParams), _P]),
+    "pt_temporal_params_default": (None, [C.POINTER(TemporalParams)]),
+    "pt_temporal_create": (_I, [_I, _I, C.POINTER(TemporalParams), C.POINTER(_P)]),
+    "pt_temporal_destroy": (_I, [_P]),
+    "pt_temporal_reset": (_I, [_P]),
+    "pt_temporal_info": (_I, [_P, _IP, _FP, _IP]),
+    "pt_temporal_frame": (_I, [_P, C.POINTER(Camera), _P, _F, _P, _P, _P, _P]),
+    "pt_temporal_resolve": (_I, [_P, _P, _P, _P, _P]),
+    "pt_temporal_frame_host": (_I, [_P, C.POINTER(Camera), _P, _F, _P, _P, _P]),
+    "pt_temporal_get": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "pt_temporal_frame_ctx": (_I, [_P, _P, _F, _P]),
+    "pt_temporal_image": (_I, [_P, C.POINTER(DenoiseVarParams), _P, _P, _P]),
 }
 
 _lib = None
@@ -231,11 +254,14 @@ def _preload_torch() -> None:
 
 # Entry points an older library may lack when PT_AMD_LIB times it beside this tree (the shipped
 # library has them all; pt_ctx_room_info: the A/B against the build before the room bound; the
-# variance entry points: the A/B against the build before them).
+# variance entry points and pt_temporal_*: the A/B against the builds before them).
 _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_moments_create",
              "pt_moments_destroy", "pt_moments_reset", "pt_moments_update", "pt_moments_info", "pt_moments_variance",
              "pt_moments_get", "pt_denoise_var_params_default", "pt_denoiser_run_var", "pt_denoise_var_host",
-             "pt_track_variance", "pt_variance_update", "pt_variance_info", "pt_get_variance", "pt_denoise_image_var"}
+             "pt_track_variance", "pt_variance_update", "pt_variance_info", "pt_get_variance", "pt_denoise_image_var",
+             "pt_temporal_params_default", "pt_temporal_create", "pt_temporal_destroy", "pt_temporal_reset",
+             "pt_temporal_info", "pt_temporal_frame", "pt_temporal_resolve", "pt_temporal_frame_host", "pt_temporal_get",
+             "pt_temporal_frame_ctx", "pt_temporal_image"}
 
 
 def lib() -> C.CDLL:

@@ -58,5 +58,11 @@ int denoise_var_check(const pt_denoise_var_params* p, float samples);
 // pt_moments: the argument checks of pt_moments_update / pt_moments_variance that need no device
 int moments_update_check(const pt_moments* m, float batch_samples);
 int moments_variance_check(const pt_moments* m, float samples);
+// pt_temporal (pt_temporal.hip): the case a frame takes (PT_TEMPORAL_*; < 0: the negated error of its
+// argument checks, no device needed), and the object's own planes a frame of that case writes its
+// G-buffer and albedo to (a producer fills them and passes them to pt_temporal_frame: no copy)
+int temporal_case(const pt_temporal* t, const pt_camera* cam, float samples);
+int temporal_staging(pt_temporal* t, int kind, float** gA, float** gB, float** alb);
+int temporal_size(const pt_temporal* t, int32_t* width, int32_t* height);
 
 }  // namespace pt

@@ -3397,6 +3397,7 @@ struct pt_ctx {
     pt_moments* mom = nullptr;
     float* mom_g = nullptr;
     bool mom_g_valid = false;
+    pt_camera scene_cam{};   // the scene camera the context was created with (pt_temporal_frame_ctx)
 
     ~pt_ctx() {
         if (mom) (void)pt_moments_destroy(mom);
@@ -4578,6 +4579,7 @@ int pt_create(const pt_scene* scene, const pt_flags* flags, const pt_shard* shar
     }
     A.cam.pl[0] = cam.pixel_length[0];
     A.cam.pl[1] = cam.pixel_length[1];
+    c->scene_cam = cam;
     A.cam.res[0] = W;
     A.cam.res[1] = H;
     A.tile = TileDev{W, sh.rank, sh.world, (int)npix, sh.spp, (int)P, S.depth, 1, 0};
@@ -5420,6 +5422,31 @@ int pt_denoise_image_var(pt_ctx* c, float samples, const pt_denoise_var_params* 
     if (rc) return rc;
     if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_denoise_image_var: ") + hipGetErrorString(e));
     return PT_OK;
+}
+
+// ---- temporal reprojection ----------------------------------------------------
+// One frame of a pt_temporal from this context: the accumulator in place, and for a frame that is not
+// of the stored view a fresh first-hit G-buffer written straight into the object's planes.
+int pt_temporal_frame_ctx(pt_temporal* t, pt_ctx* c, float samples, void* stream) {
+    if (!t || !c) return pt::fail(PT_ERR_ARG, "null argument");
+    if (c->args.tile.world > 1) return pt::fail(PT_ERR_ARG, "pt_temporal_frame_ctx needs the whole image (world == 1)");
+    int32_t tw = 0, th = 0;
+    if (int rc = pt::temporal_size(t, &tw, &th)) return rc;
+    const int W = c->args.tile.W;
+    if (tw != W || (int64_t)tw * th != (int64_t)c->args.tile.npix)
+        return pt::fail(PT_ERR_ARG, "the temporal history and the context differ in size");
+    const int kind = pt::temporal_case(t, &c->scene_cam, samples);
+    if (kind < 0) return -kind;
+    const hipStream_t st = (hipStream_t)stream;
+    float *gA = nullptr, *gB = nullptr, *alb = nullptr;
+    if (int rc = pt::temporal_staging(t, kind, &gA, &gB, &alb)) return rc;
+    if (kind != PT_TEMPORAL_SAME_VIEW) {
+        if (int rc = pt_gbuffer(c, gA, gB, alb, nullptr, st)) return rc;   // (waits for the finalize, marks the context)
+    } else if (int rc = wait_finalize(c, st)) {
+        return rc;
+    }
+    if (int rc = pt_temporal_frame(t, &c->scene_cam, c->args.image, samples, gA, gB, alb, st)) return rc;
+    return mark_ctx(c, st);
 }
 
 int pt_stats(pt_ctx* c, pt_stats_t* out) {

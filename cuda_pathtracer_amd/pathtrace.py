@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._native import DenoiseParams, DenoiseVarParams, check_pt, lib  # noqa: F401
+from ._native import DenoiseParams, DenoiseVarParams, TemporalParams, check_pt, lib  # noqa: F401
 
 SPHERE, CUBE, MESH = 0, 1, 2
 
@@ -501,6 +501,85 @@ def denoise_variance(image: np.ndarray, samples: float, variance: np.ndarray, gb
                                        ga.ctypes.data, gb.ctypes.data, al.ctypes.data, C.byref(prm), out.ctypes.data,
                                        ovar.ctypes.data if return_variance else None))
     return (out, ovar) if return_variance else out
+
+
+class TemporalHistory:
+    """pt_temporal: the denoiser's history of a full (height, width) image across camera moves
+    (DESIGN.md §12).  It belongs to no context: feed it a frame after every pass, from whichever
+    PathTracer renders the current camera, and take the image to show from image()."""
+
+    CASES = {0: None, 1: "empty", 2: "same_view", 3: "new_view"}   # PT_TEMPORAL_*
+
+    def __init__(self, width: int, height: int, params: "N.TemporalParams | None" = None):
+        self.width, self.height = int(width), int(height)
+        self._h = C.c_void_p()
+        check_pt(lib().pt_temporal_create(self.width, self.height, C.byref(params) if params is not None else None,
+                                          C.byref(self._h)))
+
+    def free(self) -> None:
+        if self._h is not None and self._h.value:
+            check_pt(lib().pt_temporal_destroy(self._h))
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        """Forget the history: the next frame starts from nothing (pt_temporal_reset)."""
+        check_pt(lib().pt_temporal_reset(self._h))
+
+    def info(self) -> dict:
+        n, bs, k = C.c_int32(), C.c_float(), C.c_int32()
+        check_pt(lib().pt_temporal_info(self._h, C.byref(n), C.byref(bs), C.byref(k)))
+        return {"frames": int(n.value), "batch_samples": float(bs.value), "last_case": self.CASES[int(k.value)]}
+
+    def frame(self, tracer: PathTracer, samples: float, stream=None) -> None:
+        """One frame from a world == 1 context of this size whose accumulator holds `samples` samples
+        (pt_temporal_frame_ctx); the context may be freed afterwards."""
+        check_pt(lib().pt_temporal_frame_ctx(self._h, tracer._h, float(samples), _stream_ptr(stream)))
+
+    def frame_arrays(self, camera: "N.Camera", image: np.ndarray, samples: float, gbuffer: dict) -> None:
+        """The same from host arrays (pt_temporal_frame_host): the camera (Scene.camera()), the
+        accumulated (H, W, 3) image and the planes of PathTracer.gbuffer() made with that camera."""
+        shape = (self.height, self.width)
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        if img.shape != shape + (3,):
+            raise ValueError(f"image shape {img.shape} != {shape + (3,)}")
+        mat = np.ascontiguousarray(gbuffer["mat"], dtype=np.int32).view(np.float32)
+        ga = _plane4(gbuffer["normal"], mat, shape)
+        gb = _plane4(gbuffer["position"], np.asarray(gbuffer["t"], np.float32), shape)
+        al = _plane4(gbuffer["albedo"], np.zeros(shape, np.float32), shape)
+        check_pt(lib().pt_temporal_frame_host(self._h, C.byref(camera), img.ctypes.data, float(samples), ga.ctypes.data,
+                                              gb.ctypes.data, al.ctypes.data))
+
+    def image(self, var_params: "N.DenoiseVarParams | None" = None, return_variance: bool = False,
+              return_history: bool = False):
+        """The history's image, (H, W, 3) float32 per-sample radiance (tonemap(..., 1.0) writes it): the
+        resolved mean, or with var_params the variance-guided filter's output on it (pt_temporal_image).
+        return_variance adds the (H, W) variance of its luminance, return_history the (H, W) history
+        length in samples."""
+        shape = (self.height, self.width)
+        out = np.empty(shape + (3,), np.float32)
+        var = np.empty(shape, np.float32) if return_variance else None
+        his = np.empty(shape, np.float32) if return_history else None
+        check_pt(lib().pt_temporal_image(self._h, C.byref(var_params) if var_params is not None else None,
+                                         out.ctypes.data, var.ctypes.data if return_variance else None,
+                                         his.ctypes.data if return_history else None))
+        res = (out,) + ((var,) if return_variance else ()) + ((his,) if return_history else ())
+        return res if len(res) > 1 else out
+
+    def _planes(self) -> dict:
+        """The state as it stands (pt_temporal_get; for tests): mean (H, W, 3), h (H, W), mu (H, W, 2),
+        gA, gB, albedo (H, W, 4) and prev (H, W, 3)."""
+        s = (self.height, self.width)
+        h0, ga, gb, al = (np.empty(s + (4,), np.float32) for _ in range(4))
+        h1, pv = np.empty(s + (2,), np.float32), np.empty(s + (3,), np.float32)
+        check_pt(lib().pt_temporal_get(self._h, h0.ctypes.data, h1.ctypes.data, ga.ctypes.data, gb.ctypes.data,
+                                       pv.ctypes.data, al.ctypes.data))
+        return {"mean": h0[..., :3].copy(), "h": h0[..., 3].copy(), "mu": h1, "gA": ga, "gB": gb, "prev": pv, "albedo": al}
 
 
 def tonemap(image: np.ndarray, samples: float) -> np.ndarray:

@@ -33,7 +33,8 @@ from pathlib import Path
 
 import numpy as np
 
-from .pathtrace import GuiDataContainer, PathTracer, Scene, save_image, tonemap
+from .pathtrace import (DenoiseVarParams, GuiDataContainer, PathTracer, Scene, TemporalHistory, save_image,
+                        tonemap)
 
 F32 = np.float32
 PI = F32(3.1415926535897932384626422832795028841971)   # utilities.h PI (a float)
@@ -56,11 +57,12 @@ class PreviewSession:
     """main.cpp's interactive state and callbacks for one scene (display-free).
 
     tracer_factory(scene, gui) -> a PathTracer-like context (pathtraceInit); read_preview(ctx, it)
-    -> the (H, W, 4) uint8 PBO contents for `it` accumulated iterations.  The defaults render on the
-    current HIP device; tests substitute both to drive the state machine on the CPU."""
+    -> the (H, W, 4) uint8 PBO contents for `it` accumulated iterations; history_factory(width, height)
+    -> a TemporalHistory-like object (the `denoise_temporal` setting).  The defaults render on the
+    current HIP device; tests substitute them to drive the state machine on the CPU."""
 
     def __init__(self, scene: Scene, gui: GuiDataContainer | None = None, out_dir: str | None = None,
-                 tracer_factory=None, read_preview=None):
+                 tracer_factory=None, read_preview=None, history_factory=None):
         self.scene = scene
         cam = scene.camera()
         self.width, self.height = int(cam.res[0]), int(cam.res[1])
@@ -95,6 +97,16 @@ class PreviewSession:
         # tracks the variance while it is on (_tracking: the current context has been told to)
         self.denoise_variance = False
         self._tracking = False
+        # panel: show the temporally reprojected, variance-filtered image (TemporalHistory).  The history
+        # belongs to the session, not to a context: it survives the restart a camera change causes.
+        self.denoise_temporal = False
+        self._history = None
+        self._history_factory = history_factory or (lambda w, h: TemporalHistory(w, h))
+        self._temporal_stats = {"frames": 0, "mean_history": 0.0}
+        # The history takes batches of one sample.  Switched on in a context that has already accumulated
+        # k samples, it is fed what that context accumulates from then on: (k, the accumulator at k, the
+        # context's G-buffer, its camera), until the next context starts (None: the whole accumulator).
+        self._history_base = None
         self.lock = threading.RLock()
 
     # ---- callbacks (main.cpp:189-271) --------------------------------------------------------
@@ -155,6 +167,10 @@ class PreviewSession:
                 self.denoise = bool(value)
             elif name == "denoise_variance":   # display only too; tracking starts at the next iteration
                 self.denoise_variance = bool(value)
+            elif name == "denoise_temporal":   # display only; the history starts with the next iteration
+                self.denoise_temporal = bool(value)
+                if not self.denoise_temporal:
+                    self._free_history()
             elif name in GENERAL_SETTINGS or name in ("SSAA", "DoF"):
                 setattr(self.gui, name, bool(value))
             elif name in SLIDERS:
@@ -171,6 +187,8 @@ class PreviewSession:
             if self.done:
                 return
             t0 = time.perf_counter()
+            if self.visual_changed and self._history is not None:
+                self._history.reset()   # (another image: a camera change alone keeps the history)
             if self.camchanged or self.visual_changed:
                 self.iteration = 0
                 self.scene.set_orbit(float(self.phi), float(self.theta), float(self.zoom), self.look_at)
@@ -180,17 +198,22 @@ class PreviewSession:
                 self._free()
                 self.ctx = self._factory(self.scene, self.gui)
                 self._tracking = False
+                self._history_base = None
             if self.iteration < self.iterations:
                 if self.denoise_variance != self._tracking:   # from the accumulator as it stands: no restart
                     self.ctx.track_variance(self.denoise_variance)
                     self._tracking = self.denoise_variance
+                if self.denoise_temporal and self._history is None and self.iteration > 0:
+                    self._history_base = (self.iteration, self.ctx.image(), self.ctx.gbuffer(), self.scene.camera())
                 self.iteration += 1
                 # pathtrace(pbo, frame, iteration): InitDataContainer's flags, one iteration, the PBO
                 self.ctx.set_flags(self.gui)
                 self.ctx.render_pass(self.iteration)
                 if self._tracking:
                     self.ctx.variance_update()
-                if self.denoise or self.denoise_variance:
+                if self.denoise_temporal:
+                    self.rgba = self._temporal_preview()
+                elif self.denoise or self.denoise_variance:
                     self.rgba = self._denoised_preview()
                 else:
                     self.rgba = self._read(self.ctx, self.iteration)
@@ -217,10 +240,35 @@ class PreviewSession:
             img = self.ctx.denoised_variance(float(self.iteration))
         else:
             img = self.ctx.denoised(float(self.iteration))
+        return self._pbo_of(img)
+
+    def _pbo_of(self, img: np.ndarray) -> np.ndarray:
         rgb = tonemap(img, 1.0)[:, ::-1]
         out = np.zeros((self.height, self.width, 4), np.uint8)
         out[..., :3] = rgb
         return out
+
+    def _temporal_preview(self) -> np.ndarray:
+        """One frame of the pass just rendered into the session's history (created at the first use),
+        and the PBO contents of its variance-filtered image."""
+        if self._history is None:
+            self._history = self._history_factory(self.width, self.height)
+        if self._history_base is None:
+            self._history.frame(self.ctx, self.iteration)
+        else:   # the samples since the box was switched on (the accumulator's gain: the render is untouched)
+            k, base, gbuffer, camera = self._history_base
+            self._history.frame_arrays(camera, self.ctx.image() - base, self.iteration - k, gbuffer)
+        img, his = self._history.image(DenoiseVarParams.default(), return_history=True)
+        self._temporal_stats = {"frames": int(self._history.info()["frames"]), "mean_history": float(np.mean(his))}
+        return self._pbo_of(img)
+
+    def _free_history(self) -> None:
+        if self._history is not None:
+            if hasattr(self._history, "free"):
+                self._history.free()
+            self._history = None
+        self._history_base = None
+        self._temporal_stats = {"frames": 0, "mean_history": 0.0}
 
     def _free(self) -> None:
         if self.ctx is not None:
@@ -241,6 +289,7 @@ class PreviewSession:
     def close(self) -> None:
         with self.lock:
             self._free()
+            self._free_history()
             self._dbuf = None
 
     # ---- what the window shows ----------------------------------------------------------------
@@ -257,13 +306,15 @@ class PreviewSession:
         with self.lock:
             ft = sum(self._frame_times) / len(self._frame_times) if self._frame_times else 0.0
             cam = self.scene.camera()
+            extra = {"temporal": dict(self._temporal_stats)} if self.denoise_temporal else {}
             return {
-                "title": self.title(), "iteration": self.iteration, "iterations": self.iterations,
+                **extra, "title": self.title(), "iteration": self.iteration, "iterations": self.iterations,
                 "done": self.done, "closed": self.should_close,
                 "traced_depth": self.traced_depth,   # "Traced Depth %d"
                 "ms_per_frame": ft * 1e3, "fps": (1.0 / ft) if ft > 0 else 0.0,
                 "settings": {**{k: getattr(self.gui, k) for k in GENERAL_SETTINGS + VISUAL_SETTINGS},
-                             "denoise": self.denoise, "denoise_variance": self.denoise_variance},
+                             "denoise": self.denoise, "denoise_variance": self.denoise_variance,
+                             "denoise_temporal": self.denoise_temporal},
                 "camera": {"phi": float(self.phi), "theta": float(self.theta), "zoom": float(self.zoom),
                            "look_at": [float(v) for v in self.look_at],
                            "position": [float(v) for v in cam.position[:3]]},
@@ -309,7 +360,8 @@ fieldset{border:1px solid #555;margin:0 0 8px 0} input[type=range]{width:160px}<
 <label><input type="checkbox" id="sortbyMaterial"> Sort by material (can harm performance)</label><br>
 <label><input type="checkbox" id="useThrustPartition"> Use thrust library for path termination</label><br>
 <label><input type="checkbox" id="denoise"> Show the denoised image (edge-avoiding a-trous filter)</label><br>
-<label><input type="checkbox" id="denoise_variance"> Show the variance-guided denoised image (tracks per-pixel variance)</label></fieldset>
+<label><input type="checkbox" id="denoise_variance"> Show the variance-guided denoised image (tracks per-pixel variance)</label><br>
+<label><input type="checkbox" id="denoise_temporal"> Keep the denoiser's history across camera moves (temporal reprojection)</label></fieldset>
 <fieldset><legend>Visual settings</legend>
 <label><input type="checkbox" id="SSAA"> Enable stochastic sampled antialiasing</label><br>
 <label><input type="checkbox" id="DoF"> Enable DoF effects</label><br>
@@ -328,7 +380,7 @@ img.addEventListener('mousemove',e=>{const p=pos(e);post({kind:'move',x:p.x,y:p.
 img.addEventListener('contextmenu',e=>e.preventDefault());
 window.addEventListener('keydown',e=>{const k=e.key==='Escape'?'ESCAPE':e.key===' '?'SPACE':e.key.toUpperCase();
  if(['ESCAPE','SPACE','S'].includes(k)){e.preventDefault();post({kind:'key',key:k});}});
-for(const id of ['russianRoulette','sortbyMaterial','useThrustPartition','denoise','denoise_variance','SSAA','DoF'])
+for(const id of ['russianRoulette','sortbyMaterial','useThrustPartition','denoise','denoise_variance','denoise_temporal','SSAA','DoF'])
  document.getElementById(id).addEventListener('change',e=>post({kind:'setting',name:id,value:e.target.checked}));
 for(const id of ['aperture','focal_len'])
  document.getElementById(id).addEventListener('input',e=>post({kind:'setting',name:id,value:parseFloat(e.target.value)}));

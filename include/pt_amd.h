@@ -467,6 +467,65 @@ int pt_variance_info(const pt_ctx* c, int32_t* on, int32_t* batches, float* batc
 int pt_get_variance(pt_ctx* c, float samples, float* host_var);
 int pt_denoise_image_var(pt_ctx* c, float samples, const pt_denoise_var_params* p, float* host_out_rgb);
 
+/* ---- temporal reprojection: denoiser history across camera moves ---------- */
+/* A history of a full image (width x height, world == 1 pixel order) that needs no context and outlives
+ * any.  Per pixel: the per-sample mean colour (divided by alb where alb.k >= 2^-10 when demodulating)
+ * with the history length h in samples, and weighted means of lum(c) and lum(c)^2 over the frames.  The
+ * object also keeps the G-buffer, albedo and camera of the frame the history belongs to and the
+ * accumulator as last seen.  The planes are allocated at the first frame: argument errors (PT_ERR_ARG)
+ * are found before any device call.
+ *   max_history  clamp of h in samples (0: unbounded; finite, >= 0, and at least one batch)
+ *   min_ndot     a history tap is dropped when dot(N_p, N_q) < min_ndot (finite, in [-1, 1])
+ *   plane_tol    ... or when |dot(N_p, P_q - P_p)| > plane_tol * t_p (finite, >= 0)
+ *   demodulate   default 1
+ *   min_frames   where h < min_frames * batch the resolved variance is spatial (0..2^20; default 4) */
+typedef struct pt_temporal_params {
+    float max_history;            /* default 32 (DESIGN.md §12's grid) */
+    float min_ndot, plane_tol;    /* defaults 0.9, 0.02 */
+    int32_t demodulate;
+    int32_t min_frames;
+    int32_t reserved[3];
+} pt_temporal_params;
+void pt_temporal_params_default(pt_temporal_params* p);
+typedef struct pt_temporal pt_temporal;
+#define PT_TEMPORAL_EMPTY 1       /* pt_temporal_info's last_case (0: no frame since the last reset) */
+#define PT_TEMPORAL_SAME_VIEW 2
+#define PT_TEMPORAL_NEW_VIEW 3
+int pt_temporal_create(int32_t width, int32_t height, const pt_temporal_params* params, pt_temporal** out); /* NULL: defaults */
+int pt_temporal_destroy(pt_temporal* t);
+int pt_temporal_reset(pt_temporal* t);                      /* the next frame finds no history */
+int pt_temporal_info(const pt_temporal* t, int32_t* frames, float* batch_samples, int32_t* last_case);
+/* One frame: the accumulator d_rgb of `samples` samples (finite, > 0), its G-buffer planes and albedo
+ * (npix float4 each, as pt_gbuffer writes them) and the camera they were made with.  Device pointers,
+ * asynchronous on `stream` (the caller orders the calls of one object).  Empty (first frame since a
+ * reset): batch b = samples, c = rgb / samples.  Same view (cam byte-equal to the stored camera and
+ * samples larger than the last frame's): b = samples - the last frame's, c = (rgb - prev) / b, in place;
+ * the planes passed in are not read.  New view (anything else): b = samples, c = rgb / samples, and each
+ * pixel takes the history of the four bilinear taps around its position in the stored view that lie on
+ * its surface.  b must equal the first frame's since the last reset (PT_ERR_ARG otherwise). */
+int pt_temporal_frame(pt_temporal* t, const pt_camera* cam, const float* d_rgb, float samples, const float* d_gA,
+                      const float* d_gB, const float* d_alb, void* stream);
+/* d_out_rgb (W*H float3): the mean, remodulated: per-sample radiance (pt_denoiser_run_var's rgb with
+ * samples = 1).  d_out_var (W*H): the variance of lum(mean): max(0, mu2 - mu1^2) * b / h where
+ * h >= min_frames * b, else the variance of lum(mean) over the 5 x 5 neighbours of the same material; 0
+ * on a miss.  d_out_h (W*H): h.  Any may be NULL; they must not alias.  Needs a frame (PT_ERR_ARG). */
+int pt_temporal_resolve(pt_temporal* t, float* d_out_rgb, float* d_out_var, float* d_out_h, void* stream);
+/* Host arrays, synchronous (for tests and the Python functions).  pt_temporal_get: the planes of the
+ * history as they stand, H0 (npix float4: mean, h), H1 (npix float2), gA, gB, prev (npix float3), alb;
+ * any may be NULL. */
+int pt_temporal_frame_host(pt_temporal* t, const pt_camera* cam, const float* rgb, float samples, const float* gA,
+                           const float* gB, const float* alb);
+int pt_temporal_get(pt_temporal* t, float* h_H0, float* h_H1, float* h_gA, float* h_gB, float* h_prev_rgb, float* h_alb);
+/* A frame from a world == 1 context of the object's size (PT_ERR_ARG otherwise): its accumulator of
+ * `samples` samples, a fresh first-hit G-buffer (none for a same-view frame) and the scene camera it was
+ * created with.  Orders itself like pt_copy_image.  The object keeps nothing of the context. */
+int pt_temporal_frame_ctx(pt_temporal* t, pt_ctx* c, float samples, void* stream);
+/* Resolve, then with var_params pt_denoiser_run_var on the resolved image and variance (samples = 1),
+ * then copy to the host: host_rgb (W*H float3), host_var (W*H; the filtered image's with var_params),
+ * host_h (W*H); any may be NULL, not all.  Synchronous. */
+int pt_temporal_image(pt_temporal* t, const pt_denoise_var_params* var_params, float* host_rgb, float* host_var,
+                      float* host_h);
+
 #ifdef __cplusplus
 }
 #endif
