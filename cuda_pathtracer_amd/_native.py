@@ -175,6 +175,7 @@ SIGNATURES = {
     "pt_set_flags": (_I, [_P, C.POINTER(Flags)]),
     "pt_ctx_cmask_info": (_I, [_P, _IP, C.POINTER(C.c_double), _IP]),
     "pt_ctx_room_info": (_I, [_P, _IP, _IP, _FP, _FP]),
+    "pt_ctx_depart_counts": (_I, [_P] + [C.POINTER(C.c_uint64)] * 3),
     "pt_ctx_counters": (_I, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pt_ctx_stream_info": (_I, [_P] + [C.POINTER(C.c_int32)] * 5),
     "pt_ctx_walk_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_double)]),
@@ -254,8 +255,9 @@ def _preload_torch() -> None:
 
 # Entry points an older library may lack when PT_AMD_LIB times it beside this tree (the shipped
 # library has them all; pt_ctx_room_info: the A/B against the build before the room bound; the
-# variance entry points and pt_temporal_*: the A/B against the builds before them).
-_OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_moments_create",
+# variance entry points and pt_temporal_*: the A/B against the builds before them;
+# pt_ctx_depart_counts: the A/B against the build before the room's departure claim).
+_OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_ctx_depart_counts", "pt_moments_create",
              "pt_moments_destroy", "pt_moments_reset", "pt_moments_update", "pt_moments_info", "pt_moments_variance",
              "pt_moments_get", "pt_denoise_var_params_default", "pt_denoiser_run_var", "pt_denoise_var_host",
              "pt_track_variance", "pt_variance_update", "pt_variance_info", "pt_get_variance", "pt_denoise_image_var",

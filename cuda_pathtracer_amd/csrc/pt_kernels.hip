@@ -65,6 +65,11 @@ struct Ctl {            // per-parity control block (32 B)
 struct DevStats {
     unsigned long long segments, passes, bounce_live[64];
     uint32_t err, bound_mismatch;
+    // PT_AMD_VERIFY_BOUNDS=1 only (the CHECK / VERIFY instantiations; pt_ctx_depart_counts):
+    uint32_t room_depart;   // rays whose wall behind is a miss by its tight plane alone (bound_room_tagged)
+    uint32_t loop_zero;     // (ray, loop cube) pairs left as candidates with bound 0 (bound_wbox_tagged)
+    uint32_t loop_depart;   // of those, the origin beyond the cube's own widened slab and moving away
+    uint32_t pad_;
 };
 
 struct SceneDev {
@@ -94,6 +99,8 @@ struct SceneDev {
     float room_out[6];     // the box of the walls' widened world boxes, (lowest wlo_a, highest whi_a) at [2a]
     uint32_t room_tag[6];  // face 2a (-a), 2a + 1 (+a): the wall's geom index, or +inf's bits (a miss) without one
     float room_wback;      // the largest DGeom::wback of the walls
+    float room_in[6];      // the walls' tight facing planes (Lin_a, Hin_a) at [2a]: the hull of the widened cube
+                           // without the pad, rounded outward (+inf / -inf: no wall, or PT_AMD_ROOM_DEPART=0)
 };
 struct CamDev {
     float pos[3], view[3], up[3], right[3], pl[2];
@@ -704,8 +711,59 @@ __device__ __forceinline__ uint32_t tag_bound(float v, uint32_t i) {
 //  - Pass 2 tests a candidate whenever its bound does not exceed the best exact hit, so weaker valid
 //    bounds and more candidates cannot change the selected hit (minimum t, lowest index on ties).
 // r_a = +-inf (d_a = +-0) needs no case of its own: the signs above are those of the products.
-template <class Ins>
-__device__ __forceinline__ void bound_room_tagged(const SceneDev& S, f3 o, f3 r, float rlt, Ins&& insert_tagged) {
+//
+// The departure claim.  A ray that has just left a wall starts 1e-4 (1 + cos) from its face (scatterRay's
+// 1e-4 n after getPointOnRay's 1e-4 pull-back), inside the wall's padded slab (the pad of update_bounds
+// brings the facing plane 0.8 .. 1.6e-4 out on Cornell), so min(tL, tH) < 0 does not hold and the wall
+// stayed a candidate with bound 0: an exact test that always misses, run by the whole wave.  The wall
+// behind is therefore ALSO a miss when
+//        Lin_a < o_a  and  o_a < Hin_a        (two float comparisons, no arithmetic on the ray)
+// with the walls' TIGHT facing planes (room_in): Lin_a >= every a-coordinate of the -a wall's widened cube
+// W (the image, under the exact inverse of the float matrix `inv`, of [slo, shi]), Hin_a <= those of the
+// +a wall's; for a face without a wall the infinity that leaves the other comparison alone.  The wall
+// behind is the -a wall when r_a's sign bit is clear and the +a wall when it is set, as above, so the
+// comparison that matters is o_a > Lin_a resp. o_a < Hin_a; the other one only withholds the claim where
+// min(tL, tH) < 0 makes it anyway (the origin in or past the opposite wall), and withholding is always safe.
+//  (a) The planes hold W.  update_bounds takes the hull of W's eight corners under X = inv's linear part
+//      inverted in double: the hull of an affine image is the hull of the corners' images for ANY matrix,
+//      also one the 1e-4 alignment test lets through with its -4.4e-8 cosines (the hull is then wider
+//      than the cube by that share of the long axes, nothing else changes).  The double values carry
+//      a few 2^-53 of the coordinates; they are moved out by 2^-40 (R + 1) and the float is taken one
+//      step outward from the nearest, so it lies beyond them by more than that rounding.
+//  (b) The ray misses W in exact arithmetic.  rcp keeps the sign of d_a (rcp(+-0) and rcp of a flushed
+//      denormal are +-inf of that sign), so a clear sign bit means d_a >= +0: every point o + s d, s >= 0,
+//      has a-coordinate >= o_a > Lin_a >= W's (d_a = +-0, r_a = +-inf: the coordinate stays o_a);
+//      likewise below Hin_a for a set sign bit.  Nothing is rounded: o_a and the planes are the floats
+//      compared.
+//  (c) A ray that misses W in exact arithmetic makes the reference's float boxIntersectionTest return -1,
+//      and this uses mu alone, not the pad.  Suppose the reference reports a hit: its tmax > 0 and
+//      tmax >= tmin >= every positive near parameter, so at t* = tmax all three axes k have
+//      near_k <= t* <= far_k (an axis with qd_k = 0 needs |qo_k| <= 0.5 for that, and a 0/0 axis puts no
+//      condition but has |qo_k| = 0.5).  The quotients are correctly rounded, so the float ray's point
+//      p = qo + t* qd lies in the unit cube up to the rounding of (-+0.5 - qo_k) and of the quotient:
+//      |p_k| <= 0.5 + 5 ulp (S_k + 0.5), update_bounds's count.  The exact ray at s* = t* / |qv| > 0
+//      (qv = inv's linear part applied to d in float, qd = qv / |qv|) is at q = qo' + s* qv' (primes: exact), and
+//        |q_k - p_k| <= |qo'_k - qo_k|          <= 4 ulp S_k                       (update_bounds)
+//                     + s* |qv'_k - qv_k|       <= 3 ulp sum_i |inv_ik| |s* d_i|   <= 6 ulp S_k
+//                     + t* |qv_k / |qv| - qd_k| <= 2 ulp |p_k - qo_k|              <= 4 ulp (S_k + 0.5)
+//      (|s* d_i| <= 2 R: the origin and the point in the cube both lie within R; |p_k - qo_k| <= 1 + 2 |qo_k|).
+//      Together 19 ulp (S_k + 1) < mu_k = 64 ulp (S_k + 1) (ulp = 2^-24; counted as 2^-23 still 38 < 64):
+//      q lies in W, so the exact ray meets W at s* > 0.  The near-parallel case is inside this count:
+//      where rounding gives qd_k the other sign than qv'_k (or than d_a), |qv_k| <= |qv'_k - qv_k|, so
+//      to come back from beyond W into the unit slab the float ray needs
+//      s >= (mu_k - 13 ulp (S_k + 1)) / (3 ulp sum_i |inv_ik| |d_i|) > 8 x the 2 R / |d_i| within which the
+//      other axes' far parameters end (qd is normalized: one axis has |qd_j| >= 3^-1/2, so tmax <=
+//      3^1/2 (0.5 + |qo_j|), a point within the scene): tmin > tmax, a miss.  The pad of update_bounds is
+//      not used anywhere here; it covers the rounding of the world-space slab parameters that E0 > X
+//      compares (bound_wbox_tagged), which a comparison of o_a itself does not have.
+//  (d) NaN: a NaN o_a fails both comparisons, no claim.  The claim does not read the direction's value, only
+//      which wall r_a's sign bit calls "behind"; a ray with a NaN direction component hits nothing in the
+//      reference (intersect_bounded returns before the pass), so any claim about it holds.
+// COUNT (the CHECK / VERIFY instantiations under PT_AMD_VERIFY_BOUNDS=1 only): *depart counts the rays for
+// which the tight planes made a wall a miss that min(tL, tH) < 0 alone left a candidate.
+template <bool COUNT = false, class Ins>
+__device__ __forceinline__ void bound_room_tagged(const SceneDev& S, f3 o, f3 r, float rlt, Ins&& insert_tagged,
+                                                  uint32_t* depart = nullptr) {
     float ta[3], qa[3];
     v2f t[3];
 #pragma unroll
@@ -716,6 +774,7 @@ __device__ __forceinline__ void bound_room_tagged(const SceneDev& S, f3 o, f3 r,
         ta[a] = fmaxf(fmaxf(t[a].x, t[a].y), 0.0f);
         qa[a] = fmaxf(q.x, q.y);
     }
+    bool counted = false;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float v = fmaf(ta[a], rlt, -S.room_wback);
@@ -726,8 +785,12 @@ __device__ __forceinline__ void bound_room_tagged(const SceneDev& S, f3 o, f3 r,
         const uint32_t ahead = (neg & wx) ^ wh;
         const bool past = fminf(qa[(a + 1) % 3], qa[(a + 2) % 3]) < ta[a];
         insert_tagged(tag_bound(v, 0u) | ahead | (past ? 0x7f800000u : 0u));
-        insert_tagged(fminf(t[a].x, t[a].y) < 0.0f ? 0x7f800000u : (ahead ^ wx));
+        const bool back = fminf(t[a].x, t[a].y) < 0.0f;
+        const bool left = at(o, a) > S.room_in[2 * a] && at(o, a) < S.room_in[2 * a + 1];
+        if (COUNT) counted = counted || (left && !back && (ahead ^ wx) < 0x7f800000u);
+        insert_tagged((back || left) ? 0x7f800000u : (ahead ^ wx));
     }
+    if (COUNT && depart && counted) atomicAdd(depart, 1u);
 }
 
 // Lower bound on the exact test's world distance for geom g (before the scene's absolute slack),
@@ -898,9 +961,11 @@ __device__ __forceinline__ uint32_t ng_all_mask(int n) { return n >= 32 ? ~0u : 
 #if defined(PT_DUP)
 __device__ uint32_t g_dup_sink;
 #endif
-template <bool SEL, bool PRE = false>
+// COUNT, cnt: the departure counters of the CHECK / VERIFY instantiations (DevStats::room_depart, loop_*).
+template <bool SEL, bool PRE = false, bool COUNT = false>
 __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsDev& fl, const LGeom* s_geoms, f3 ro,
-                                                 f3 rd, const MeshHit* mh = nullptr, uint32_t gmask = ~0u) {
+                                                 f3 rd, const MeshHit* mh = nullptr, uint32_t gmask = ~0u,
+                                                 DevStats* cnt = nullptr) {
     const float rl = __builtin_amdgcn_sqrtf(dot(rd, rd));
     bool plain = !(rl > 0.5f && rl < 2.0f);   // NaN / degenerate direction: the plain loop
     float t_min = kFLT_MAX;
@@ -963,11 +1028,29 @@ __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsD
         // bounces only: their gmask is all ones, the camera rays keep their masks and the loop.
         const bool room = SEL && gmask == ~0u && S.room_n > 0;
         if (room) {
-            bound_room_tagged(S, ro, invd, rlt, insert_tagged);
+            bound_room_tagged<COUNT>(S, ro, invd, rlt, insert_tagged, COUNT && cnt ? &cnt->room_depart : nullptr);
             j3 += S.room_n;
         }
         for (int j = j3; j < S.bk[4]; ++j)   // world-box cubes: packed slabs
             if ((gmask >> B[j].orig) & 1u) insert_tagged(bound_wbox_tagged(B[j], ro, invd, rlt, (uint32_t)B[j].orig));
+        if (COUNT && SEL && cnt && gmask == ~0u) {
+            // measurement only: the later bounces' (ray, loop cube) pairs that stay candidates with bound 0,
+            // and those of them whose origin is beyond the cube's own widened object-space slab on an axis
+            // along which the ray does not come back — what a departure claim for the loop could remove
+            uint32_t zero = 0u, dep = 0u;
+            for (int j = j3; j < S.bk[4]; ++j) {
+                if (bound_wbox_tagged(B[j], ro, invd, rlt, 0u) != 0u) continue;
+                const f3 qo = xform_point(B[j].inv, ro), qv = xform_vector(B[j].inv, rd);
+                bool away = false;
+                for (int k = 0; k < 3; ++k)
+                    away = away || (at(qo, k) > B[j].shi[k] && at(qv, k) >= 0.0f) ||
+                           (at(qo, k) < B[j].slo[k] && at(qv, k) <= 0.0f);
+                ++zero;
+                dep += away ? 1u : 0u;
+            }
+            if (zero) atomicAdd(&cnt->loop_zero, zero);
+            if (dep) atomicAdd(&cnt->loop_depart, dep);
+        }
         if (SEL) {
             const bool spheres = S.bk[4] < S.bk[5], oboxes = S.bk[1] < S.bk[2];
             if (spheres || oboxes) {   // per-ray reciprocals (bound_sphere_tagged, bound_obox_tagged)
@@ -1107,15 +1190,16 @@ __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsD
 // larger table is not compiled in.
 template <bool MESH, bool CHECK, bool SEL = false, bool LDSG = false>
 __device__ __forceinline__ Hit closest_hit(const SceneDev& S, const FlagsDev& fl, const LGeom* s_geoms, f3 ro, f3 rd,
-                                           uint32_t* mismatch, uint32_t gmask = ~0u) {
+                                           DevStats* stats, uint32_t gmask = ~0u) {
     if (MESH || (!LDSG && S.ngeoms > kLdsGeoms)) return intersect_scene<MESH>(S, fl, ro, rd);
-    const Hit h = intersect_bounded<SEL>(S, fl, s_geoms, ro, rd, nullptr, gmask);
+    const Hit h = intersect_bounded<SEL, false, CHECK>(S, fl, s_geoms, ro, rd, nullptr, gmask,
+                                                        CHECK && fl.verify ? stats : nullptr);
     if (CHECK && fl.verify) {
         const Hit r = intersect_scene<false>(S, fl, ro, rd);
         if (__float_as_uint(h.t) != __float_as_uint(r.t) || h.mat != r.mat ||
             __float_as_uint(h.n.x) != __float_as_uint(r.n.x) || __float_as_uint(h.n.y) != __float_as_uint(r.n.y) ||
             __float_as_uint(h.n.z) != __float_as_uint(r.n.z))
-            atomicAdd(mismatch, 1u);
+            atomicAdd(&stats->bound_mismatch, 1u);
     }
     return h;
 }
@@ -1451,7 +1535,7 @@ __global__ __launch_bounds__(kBlock) void k_trace(const KArgs A) {
                 gm = A.cmask[l0 >> 6] | A.cmask[(l1 >= l0 ? l1 : np - 1) >> 6];
                 if (l1 < l0) gm |= A.cmask[0] | A.cmask[l1 >> 6];
             }
-            const Hit h = closest_hit<MESH, true, !FIRST>(A.S, A.fl, s_geoms, p.o, p.d, &A.stats->bound_mismatch, gm);
+            const Hit h = closest_hit<MESH, true, !FIRST>(A.S, A.fl, s_geoms, p.o, p.d, A.stats, gm);
             const int it = SPP1 ? 0 : p.slot / A.tile.npix;
             const int iter = A.tile.iter_first + it;
             // key: index within the path's own iteration (k_iter_bases; see k_bounce)
@@ -2459,12 +2543,12 @@ void k_bounce(const KArgs A) {
                     const int lp0 = __builtin_amdgcn_readfirstlane(i - it_base);
                     gm = A.cmask[lp0 >> 6];
                 }
-                h = closest_hit<MESH == kMeshInline, false, !FIRST, kLdsAll>(A.S, A.fl, s_geoms, p.o, p.d, &A.stats->bound_mismatch, gm);
+                h = closest_hit<MESH == kMeshInline, false, !FIRST, kLdsAll>(A.S, A.fl, s_geoms, p.o, p.d, A.stats, gm);
 #if defined(PT_DUP) && PT_DUP == 7   // diagnostic: the camera ray's closest hit again on an opaque origin
                 if (FIRST) {
                     f3 o2 = p.o;
                     asm volatile("" : "+v"(o2.x), "+v"(o2.y), "+v"(o2.z));
-                    const Hit h2 = closest_hit<MESH == kMeshInline, false, !FIRST>(A.S, A.fl, s_geoms, o2, p.d, &A.stats->bound_mismatch, gm);
+                    const Hit h2 = closest_hit<MESH == kMeshInline, false, !FIRST>(A.S, A.fl, s_geoms, o2, p.d, A.stats, gm);
                     if (__float_as_uint(h2.t) == 0x7f7ffffeu) atomicAdd(&A.stats->bound_mismatch, 7u);
                 }
 #endif
@@ -2479,7 +2563,7 @@ void k_bounce(const KArgs A) {
                 f3 o2 = p.o;
                 asm volatile("" : "+v"(o2.x), "+v"(o2.y), "+v"(o2.z));
                 if (PT_DUP == 1) {
-                    const Hit h2 = closest_hit<false, false, true>(A.S, A.fl, s_geoms, o2, p.d, &A.stats->bound_mismatch, ~0u);
+                    const Hit h2 = closest_hit<false, false, true>(A.S, A.fl, s_geoms, o2, p.d, A.stats, ~0u);
                     if (__float_as_uint(h2.t) == 0x7f7ffffeu) atomicAdd(&A.stats->bound_mismatch, 7u);
                 } else if (PT_DUP == 2) {
                     PathReg p2 = p;
@@ -2914,7 +2998,7 @@ void k_sort_produce(const KArgs A, const SortArgs SA) {
                 gm = A.cmask[lp0 >> 6];
             }
             if (alive) {
-                h = closest_hit<MESH, VERIFY, !FIRST, LDSM && !MESH>(A.S, A.fl, s_geoms, p.o, p.d, &A.stats->bound_mismatch, gm);
+                h = closest_hit<MESH, VERIFY, !FIRST, LDSM && !MESH>(A.S, A.fl, s_geoms, p.o, p.d, A.stats, gm);
                 PathReg e = p;   // (only the verdict here; the colour below)
                 ends = lds_mats ? shade_ends(h, s_mats, e) : shade_ends(h, A.S.mats, e);
             }
@@ -3210,8 +3294,12 @@ __global__ void k_ahead_settle(float* __restrict__ image, const v4f* __restrict_
     } else if (gid == 66) {
         st->err |= ast->err;
         st->bound_mismatch += ast->bound_mismatch;
+        st->room_depart += ast->room_depart;
+        st->loop_zero += ast->loop_zero;
+        st->loop_depart += ast->loop_depart;
         ast->err = 0u;
         ast->bound_mismatch = 0u;
+        ast->room_depart = ast->loop_zero = ast->loop_depart = 0u;
     }
 }
 
@@ -3311,6 +3399,8 @@ struct pt_ctx {
     size_t ev_used = 0;
     size_t path_cap = 0;          // entries per path buffer (>= P, see pt_create)
     std::vector<DGeom> hgeoms;    // host copy of the geom table (bounds re-derived by pt_set_flags)
+    std::vector<float> wtight;    // bkind 3: the widened cube's world hull before the pad, rounded outward,
+                                  // (lo, hi) of axis r at [6 * geom + 2 * r] (update_bounds; find_room's room_in)
     uint32_t* d_cmask = nullptr;  // first-bounce geom masks, one per 64 tile pixels (build_cmask)
     DGeom* d_geoms = nullptr;
     DGeom* d_bgeoms = nullptr;    // the same geoms ordered by bound kind (SceneDev::bgeoms)
@@ -3516,6 +3606,7 @@ void find_room(pt_ctx* c) {
         S.room_pl[f] = (f & 1) ? HUGE_VALF : -HUGE_VALF;
         S.room_out[f] = (f & 1) ? -HUGE_VALF : HUGE_VALF;
         S.room_tag[f] = 0x7f800000u;
+        S.room_in[f] = (f & 1) ? -HUGE_VALF : HUGE_VALF;   // no origin is between these: no claim
     }
     const std::vector<DGeom>& G = c->hgeoms;
     const size_t n = G.size();
@@ -3595,6 +3686,16 @@ void find_room(pt_ctx* c) {
         }
         ++S.room_n;
     }
+    // The tight facing planes of bound_room_tagged's departure claim: a wall's own hull plane, and for a
+    // face without a wall the infinity that leaves the claim to the other face's plane alone (what is
+    // claimed a miss there is the missing wall, which is no candidate anyway).  PT_AMD_ROOM_DEPART=0
+    // keeps the values no origin lies between (A/B and tests; the same bits).
+    bool depart = S.room_n > 0;
+    if (const char* e = std::getenv("PT_AMD_ROOM_DEPART"))
+        if (std::atoi(e) == 0) depart = false;
+    for (int f = 0; f < 6 && depart; ++f)
+        S.room_in[f] = face[f] >= 0 ? c->wtight[6 * (size_t)face[f] + 2 * (size_t)(f >> 1) + (size_t)(~f & 1)]
+                                    : ((f & 1) ? HUGE_VALF : -HUGE_VALF);
 }
 
 // Widened bounds of the bounded closest-hit pass (bound_geom), sized from R = the largest
@@ -3606,6 +3707,7 @@ void find_room(pt_ctx* c) {
 // and the rounding of the reference's length(); abs_slack its absolute part.
 void update_bounds(pt_ctx* c, float aperture) {
     const double R = c->scene_ext + std::fabs((double)aperture) + 1e-2;
+    c->wtight.assign(6 * c->hgeoms.size(), 0.0f);
     for (DGeom& d : c->hgeoms) {
         double smax = 0.0;
         for (int a = 0; a < 3; ++a) {
@@ -3707,6 +3809,13 @@ void update_bounds(pt_ctx* c, float aperture) {
                 for (int r = 0; r < 3; ++r) {
                     d.wlo[r] = (float)(lo[r] - pad - std::ldexp(std::fabs(lo[r]), -18));
                     d.whi[r] = (float)(hi[r] + pad + std::ldexp(std::fabs(hi[r]), -18));
+                    // the hull itself, for the departure claim of bound_room_tagged: moved out by 2^-40 (R + 1)
+                    // (the rounding of X and of the sums above is a few 2^-53 of the coordinates, also where
+                    // the plane itself cancels to nearly 0), then one float further out than the nearest one
+                    const double eps = std::ldexp(R + 1.0, -40);
+                    float* tg = &c->wtight[6 * (size_t)(&d - c->hgeoms.data()) + 2 * (size_t)r];
+                    tg[0] = std::nextafter((float)(lo[r] - eps), -HUGE_VALF);
+                    tg[1] = std::nextafter((float)(hi[r] + eps), HUGE_VALF);
                 }
                 d.back = (float)(1.0002e-4 * stretch * (1.0 + 1e-5));
                 for (int r = 0; r < 3; ++r) {
@@ -4837,6 +4946,17 @@ int pt_ctx_room_info(const pt_ctx* c, int32_t* walls, int32_t* faces, float* lo,
         if (lo) lo[a] = S.room_pl[2 * a];
         if (hi) hi[a] = S.room_pl[2 * a + 1];
     }
+    return PT_OK;
+}
+
+int pt_ctx_depart_counts(pt_ctx* c, uint64_t* room, uint64_t* loop_zero, uint64_t* loop_depart) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    if (int rc = wait_ctx(c)) return rc;
+    DevStats s;
+    HIP_TRY(io_copy(c, &s, c->stats, sizeof s, hipMemcpyDeviceToHost));
+    if (room) *room = s.room_depart;
+    if (loop_zero) *loop_zero = s.loop_zero;
+    if (loop_depart) *loop_depart = s.loop_depart;
     return PT_OK;
 }
 

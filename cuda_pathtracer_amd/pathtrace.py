@@ -328,6 +328,16 @@ class PathTracer:
         return {"walls": int(n.value), "faces": [int(v) for v in faces], "lo": [float(v) for v in lo],
                 "hi": [float(v) for v in hi]}
 
+    def depart_counts(self) -> dict:
+        """PT_AMD_VERIFY_BOUNDS=1 only (pt_ctx_depart_counts): later-bounce rays whose wall behind the
+        room's tight plane alone called a miss, and the per-cube loop's zero-bound candidates (all, and
+        those the same claim could remove)."""
+        if not hasattr(lib(), "pt_ctx_depart_counts"):
+            raise N.NativeLibraryError("the loaded library (PT_AMD_LIB) predates pt_ctx_depart_counts")
+        v = [C.c_uint64() for _ in range(3)]
+        check_pt(lib().pt_ctx_depart_counts(self._h, *[C.byref(x) for x in v]))
+        return {"room": int(v[0].value), "loop_zero": int(v[1].value), "loop_depart": int(v[2].value)}
+
     def walk_info(self) -> dict:
         """Mesh scenes: 4-wide walk on/off, its exact t-cull on/off and the share of slots whose
         cull margin can pay (pt_ctx_walk_info)."""

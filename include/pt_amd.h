@@ -252,6 +252,14 @@ int pt_ctx_cmask_info(const pt_ctx* c, int32_t* on, double* empty_frac, int32_t*
  * without one) and the box between the walls' facing planes (lo[3], hi[3]; -inf / +inf on a face
  * without a wall).  Results are the same bits with or without a room (PT_AMD_ROOM=0: never one). */
 int pt_ctx_room_info(const pt_ctx* c, int32_t* walls, int32_t* faces, float* lo, float* hi);
+/* Inspection, PT_AMD_VERIFY_BOUNDS=1 only (zeros otherwise; counted by the verifying kernels of the split
+ * and the sorted pipeline since the context's last reset): room — later-bounce rays for which a room
+ * wall's tight plane alone called the wall they left a miss (the departure claim, DESIGN.md §4.1;
+ * PT_AMD_ROOM_DEPART=0: none); loop_zero — (ray, cube) pairs of the per-cube world-box loop left as
+ * candidates with bound 0; loop_depart — those of them whose origin lies beyond the cube's own widened
+ * slab with the ray not coming back (what the same claim could remove there).  Waits for the context's
+ * queued work.  Any pointer may be null. */
+int pt_ctx_depart_counts(pt_ctx* c, uint64_t* room, uint64_t* loop_zero, uint64_t* loop_depart);
 /* Mesh scenes: whether the BVH walk runs on the 4-wide layout, whether its exact t-cull is on, and
  * the share of the layout's slots whose cull margin can pay.  The cull is on when
  * that share is >= 1/4 (PT_AMD_TCULL=0/1 forces it); it never changes a result. */
