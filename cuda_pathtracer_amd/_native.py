@@ -170,6 +170,7 @@ SIGNATURES = {
     "pt_scene_get_bvh": (_I, [_P, C.POINTER(BvhNode), _I]),
     "pt_scene_bvh_quads": (_I, [_P, _P, _I, _IP, _IP]),
     "pt_scene_bvh_tcull": (_I, [_P, C.POINTER(C.c_uint32), _I, C.POINTER(C.c_double)]),
+    "pt_scene_room_info": (_I, [_P, C.POINTER(Flags), _IP, _IP, _FP, _FP]),
     "pt_create": (_I, [_P, C.POINTER(Flags), C.POINTER(Shard), C.POINTER(_P)]),
     "pt_destroy": (_I, [_P]),
     "pt_set_flags": (_I, [_P, C.POINTER(Flags)]),
@@ -254,10 +255,12 @@ def _preload_torch() -> None:
 
 
 # Entry points an older library may lack when PT_AMD_LIB times it beside this tree (the shipped
-# library has them all; pt_ctx_room_info: the A/B against the build before the room bound; the
+# library has them all; pt_ctx_room_info: the A/B against the build before the room bound;
+# pt_scene_room_info: the A/B against the build before the host-only bounds unit; the
 # variance entry points and pt_temporal_*: the A/B against the builds before them;
 # pt_ctx_depart_counts: the A/B against the build before the room's departure claim).
-_OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_ctx_depart_counts", "pt_moments_create",
+_OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
+             "pt_moments_create",
              "pt_moments_destroy", "pt_moments_reset", "pt_moments_update", "pt_moments_info", "pt_moments_variance",
              "pt_moments_get", "pt_denoise_var_params_default", "pt_denoiser_run_var", "pt_denoise_var_host",
              "pt_track_variance", "pt_variance_update", "pt_variance_info", "pt_get_variance", "pt_denoise_image_var",

@@ -33,7 +33,13 @@ DEVICE_SRCS = ["sc_kernels.hip", "sc_variants.hip", "pt_kernels.hip", "bvh_build
 # register pairs and moves: k_bounce took 79 VGPRs (6 waves/SIMD) instead of 60 (8 waves), and
 # measured 30.8k vs 32.7k Mray/s on the bench (same box, alternating runs; same bits).
 EXTRA = {"pt_kernels.hip": ["-fno-slp-vectorize"]}
-HOST_SRCS = ["pt_scene.cpp", "pt_mesh.cpp", "pt_image.cpp", "pt_jpeg.cpp"]
+HOST_SRCS = ["pt_scene.cpp", "pt_mesh.cpp", "pt_image.cpp", "pt_jpeg.cpp", "pt_bounds.cpp", "pt_bvh_layout.cpp"]
+
+
+def other_objs(without: str) -> list[Path]:
+    """The native library's objects except `without`'s: what a variant of that one source links with
+    (the test-hook and walk-counter libraries below, scripts/build_variants.sh)."""
+    return [PKG / "build" / (s + ".o") for s in DEVICE_SRCS + HOST_SRCS if s != without]
 
 
 def _run(cmd: list[str], verbose: bool) -> None:
@@ -154,7 +160,7 @@ def build_test_hooks(verbose: bool = False, force: bool = False) -> Path:
     if force or _stale(obj, [src] + headers):
         _run([HIPCC, "-x", "hip", f"--offload-arch={ARCH}", *COMMON, "-DPT_SC_TEST_HOOKS", "-I", str(ROOT / "include"),
               "-c", str(src), "-o", str(obj)], verbose)
-    others = [objdir / (s + ".o") for s in DEVICE_SRCS + HOST_SRCS if s != "sc_kernels.hip"]
+    others = other_objs("sc_kernels.hip")
     if force or _stale(TESTHOOKS_LIB, [obj] + others):
         _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(TESTHOOKS_LIB), str(obj),
               *map(str, others), "-lz"], verbose)
@@ -175,7 +181,7 @@ def build_trav_stats(verbose: bool = False, force: bool = False) -> Path:
     if force or _stale(obj, [src] + headers):
         _run([HIPCC, "-x", "hip", f"--offload-arch={ARCH}", *COMMON, *EXTRA["pt_kernels.hip"], "-DPT_TRAV_STATS",
               "-I", str(ROOT / "include"), "-c", str(src), "-o", str(obj)], verbose)
-    others = [objdir / (s + ".o") for s in DEVICE_SRCS + HOST_SRCS if s != "pt_kernels.hip"]
+    others = other_objs("pt_kernels.hip")
     if force or _stale(TRAV_LIB, [obj] + others):
         _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(TRAV_LIB), str(obj),
               *map(str, others), "-lz"], verbose)

@@ -10,13 +10,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace ptd {
+#include "pt_layout.h"
 
-constexpr float kPI = 3.1415926535897932384626422832795028841971f;       // utilities.h:12
-constexpr float kTWO_PI = 6.2831853071795864769252867665590057683943f;   // utilities.h:13
-constexpr float kSQRT_1_3 = 0.5773502691896257645091487805019574556476f; // utilities.h:14
-constexpr float kFLT_MAX = 3.402823466e+38f;
-constexpr float kFLT_EPS = 1.192092896e-07f;
+namespace ptd {
 
 struct f3 { float x, y, z; };
 __device__ __forceinline__ f3 F3(float x, float y, float z) { return f3{x, y, z}; }
@@ -101,13 +97,6 @@ __device__ __forceinline__ float gmin(float a, float b) { return a < b ? a : b; 
 __device__ __forceinline__ float gmax(float a, float b) { return a > b ? a : b; }
 __device__ __forceinline__ float at(f3 v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }
 
-// Affine 3x4 in glm column order + the exact glm w-term constants.
-//   point  (w=1): (c0 x + c1 y) + (c2 z + c3)
-//   vector (w=0): (c0 x + c1 y) + (c2 z + z3),  z3 = c3 * 0.0f (a signed zero)
-struct Affine {
-    float c[4][3];
-    float z3[3];
-};
 // Scene tables that every lane of a wave reads at the same address are accessed through the
 // constant address space so hipcc emits scalar (s_load) reads into SGPRs instead of 64 copies.
 #define PT_CONST_AS __attribute__((address_space(4)))
@@ -127,81 +116,6 @@ __device__ __forceinline__ f3 xform_vector(const M& m, f3 v) {
               (m.c[0][1] * v.x + m.c[1][1] * v.y) + (m.c[2][1] * v.z + m.z3[1]),
               (m.c[0][2] * v.x + m.c[1][2] * v.y) + (m.c[2][2] * v.z + m.z3[2]));
 }
-
-// Device copy of a Geom: what intersection needs, nothing else (176 bytes, scalar-loaded).
-struct DGeom {
-    int32_t type, material, tri_start, tri_end;
-    Affine inv;      // inverseTransform
-    Affine xf;       // transform
-    Affine itr;      // invTranspose
-    float bmin[3], bmax[3];
-    // Conservative bounds test (pt_kernels.hip bound_geom), filled by pt_create: the unit cube's
-    // slabs widened to [slo, shi] = [-0.5 - mu_a, 0.5 + mu_a], the sphere's radius^2 widened to
-    // r2w = 0.25 + kappa (mu, kappa exceed the rounding of both the exact test and the bounds
-    // test for every ray origin in the scene), and tslack < 1, the relative slack that turns a
-    // lower bound on the hit parameter into one on the reference's world distance.
-    //   A sphere ray whose origin is outside the exact sphere by more than
-    // kappa_ray = (|qo|^2 + 1) (kcs |ro|_inf + kc3) and moves away from its centre surely misses
-    // (the ray leaving the sphere it just hit; the widened radius alone cannot tell).
-    //   Axis-aligned cubes (bkind 3: the Cornell walls, incl. 90-degree rotations) are bounded by
-    // their widened WORLD box [wlo, whi] (of the exact inverse of `inv`): a 6-plane slab test on the
-    // world ray, with `back` >= 1e-4 * (largest stretch of the transform) for pointOnRay's pull-back.
-    float slo[3], shi[3];
-    float r2w, tslack;
-    float kcs, kc3;
-    float wlo[3], whi[3], back;
-    int32_t bkind;   // 0: never hit (mesh), 1: oriented cube, 2: sphere, 3: world-box cube,
-                     // 4: uniformly scaled sphere (world-space dot products)
-    int32_t orig;    // SceneDev::bgeoms rows: index of this geom in SceneDev::geoms
-    // Cubes: the world normal of each slab code (axis * 2 + sign) — boxIntersectionTest's
-    // normalize(multiplyMV(invTranspose, (n, 0))) of a unit axis vector depends on the geom and
-    // the code only, so pt_create evaluates it once with the same float32 operations (glm's
-    // association, correctly rounded sqrt and division: the same bits as the per-hit evaluation).
-    float nrm[6][3];
-    // Cubes: the tangent frame calculateRandomDirectionInHemisphere builds from each of those
-    // normals (interactions.cu:23-33: p1 = normalize(cross(n, dnn)), p2 = normalize(cross(n, p1))),
-    // also a function of (geom, code) only: frm[code] = (p1, p2), evaluated once by pt_create.
-    float frm[6][6];
-    // bkind 3: the widened world box with each axis's two planes side by side, (wlo[k], whi[k]) at
-    // wbox[2k], so one packed f32 operation (v_pk_add_f32 / v_pk_mul_f32, IEEE per component) takes
-    // both planes of an axis from one SGPR pair (pt_kernels.hip slab2)
-    float wbox[6];
-    float wback;   // bkind 3: back * SceneDev::wb_tslack rounded up (bound_wbox_tagged)
-    float pad_;
-};
-
-struct DMaterial {   // == pt_material
-    float color[3];
-    float spec_exponent;
-    float spec_color[3];
-    float has_reflective, has_refractive, ior, emittance;
-    int32_t texture_id;
-};
-
-struct DTexture {
-    int32_t width, height, components, pad;
-    const uint8_t* data;
-};
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-// Triangle hot data, 48 bytes = three 16-byte loads: (v0, id bits), (e1, 0), (e2, 0).  The edges
-// e1 = v1 - v0, e2 = v2 - v0 are computed on the host with the same single subtraction glm
-// performs, so the per-test arithmetic is unchanged.
-struct alignas(16) DTri {
-    v4f a, b, c;
-};
-struct DTriAttr {    // read once for the closest hit
-    float n[3][3];
-    float uv[3][2];
-};
-// BVH node, 32 bytes = two 16-byte loads: lo = (bmin, meta), hi = (bmax, link)
-//   leaf:     meta = sub_areas (> 0),  link = first triangle
-//   interior: meta = -(axis + 1),      link = right child (the left child is this node + 1)
-struct alignas(16) DNode {
-    v4f lo, hi;
-};
 
 // ---- RNG: thrust::default_random_engine (minstd_rand) seeded like makeSeededRandomEngine ----
 __device__ __forceinline__ uint32_t utilhash(uint32_t a) {   // intersections.h:13-22

@@ -1,10 +1,12 @@
 // Internal host-side types shared by the scene loader, mesh/BVH builder and render context.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/pt_amd.h"
+#include "pt_layout.h"
 
 namespace pt {
 
@@ -64,5 +66,41 @@ int moments_variance_check(const pt_moments* m, float samples);
 int temporal_case(const pt_temporal* t, const pt_camera* cam, float samples);
 int temporal_staging(pt_temporal* t, int kind, float** gA, float** gB, float** alb);
 int temporal_size(const pt_temporal* t, int32_t* width, int32_t* height);
+
+inline float bits_to_float(int32_t v) {
+    float f;
+    std::memcpy(&f, &v, 4);
+    return f;
+}
+inline int32_t __float_as_int_host(float f) {
+    int32_t v;
+    std::memcpy(&v, &f, 4);
+    return v;
+}
+
+// Scene preparation of the bounded closest hit (pt_bounds.cpp; no device needed).  What a context
+// keeps on the host to re-derive the bounds when the lens changes (pt_set_flags):
+struct BoundsHost {
+    std::vector<ptd::DGeom> geoms;   // host copy of the geom table
+    std::vector<float> wtight;       // bkind 3: the widened cube's world hull before the pad, rounded outward,
+                                     // (lo, hi) of axis r at [6 * geom + 2 * r] (update_bounds; find_room's room.in)
+    double scene_ext = 0.0;          // max |coordinate| over every surface and the camera position
+    float abs_slack = 0.0f;          // SceneDev::abs_slack
+    float wb_tslack = 0.0f;          // SceneDev::wb_tslack
+    ptd::RoomDev room{};             // SceneDev::room
+};
+BoundsHost make_dgeoms(const Scene& S);
+void update_bounds(BoundsHost& B, float aperture);   // (ends with find_room)
+void find_room(BoundsHost& B);
+void bound_order(const BoundsHost& B, std::vector<ptd::DGeom>& out, int32_t bk[6]);
+void camera_masks(const BoundsHost& B, const ptd::CamDev& cam, const ptd::FlagsDev& fl, const ptd::TileDev& T,
+                  std::vector<uint32_t>& mask);
+void room_info(const ptd::RoomDev& room, int32_t* walls, int32_t* faces, float* lo, float* hi);
+// BVH layouts of the walk kernels (pt_bvh_layout.cpp; no device needed)
+std::vector<ptd::DNode> to_dnodes(const std::vector<pt_bvh_node>& bvh);
+bool make_quads(const std::vector<ptd::DNode>& nodes, std::vector<ptd::DQuad>& quads, int32_t& root_code,
+                int32_t& root_occ, std::vector<int32_t>* slot_node = nullptr);
+double build_qcull(const std::vector<ptd::DNode>& nodes, const std::vector<pt_triangle>& tris,
+                   const std::vector<int32_t>& slot_node, std::vector<uint32_t>& qcull);
 
 }  // namespace pt

@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <cstddef>
 #include <cstdio>
 #include <cmath>
 #include <cstdlib>
@@ -85,40 +86,16 @@ struct SceneDev {
     int32_t bvh_depth;     // deepest interior node (root = 0): bounds the traversal stack
     float abs_slack;       // absolute slack of the world-distance lower bounds (bound_geom)
     float wb_tslack;       // the smallest tslack of the world-box cubes (bound_wbox_tagged; DGeom::wback)
-    const struct DPair* __restrict__ pairs;   // child-pair layout of the BVH (bvh_walk_pairs)
+    const DPair* __restrict__ pairs;   // child-pair layout of the BVH (bvh_walk_pairs)
     int32_t root_code;     // code of the root (see DPair), meaningful when pairs != nullptr
     v4f root_lo, root_hi;  // root box
-    const struct DQuad* __restrict__ quads;   // 4-wide collapse of the pair tree (k_traverse4), or null
+    const DQuad* __restrict__ quads;   // 4-wide collapse of the pair tree (k_traverse4), or null
     int32_t root_qcode;    // root's code in the quad layout (quad index or leaf code)
     const float* __restrict__ tpack;   // the triangles again as packed 36-byte (v0, e1, e2): k_traverse4's task loads
     const uint32_t* __restrict__ qcull;   // exact t-cull margins of the quads' slots (build_qcull), or null: off
-    // The room (find_room, bound_room): up to six world-box cubes, one per face of the box B they
-    // enclose, bounded as one group by the later bounces.  They are bgeoms[bk[3] .. bk[3] + room_n).
-    int32_t room_n;        // walls of the room (0: no room, nothing below is read)
-    float room_pl[6];      // B, an axis's two planes side by side: (L_a, H_a) at [2a] (-inf / +inf: no wall)
-    float room_out[6];     // the box of the walls' widened world boxes, (lowest wlo_a, highest whi_a) at [2a]
-    uint32_t room_tag[6];  // face 2a (-a), 2a + 1 (+a): the wall's geom index, or +inf's bits (a miss) without one
-    float room_wback;      // the largest DGeom::wback of the walls
-    float room_in[6];      // the walls' tight facing planes (Lin_a, Hin_a) at [2a]: the hull of the widened cube
-                           // without the pad, rounded outward (+inf / -inf: no wall, or PT_AMD_ROOM_DEPART=0)
+    RoomDev room;          // the room whose walls the later bounces bound as one group (find_room), or n = 0
 };
-struct CamDev {
-    float pos[3], view[3], up[3], right[3], pl[2];
-    int32_t res[2];
-};
-struct FlagsDev {
-    int32_t rr, bvh, bbox, ssaa, dof;
-    float aperture, focal;
-    int32_t single_albedo;
-    int32_t bvh_cull;
-    int32_t claimed;   // tile schedule (lookback.h TileSeq)
-    int32_t rng_pixel; // shading RNG keyed by global pixel (pt_flags.rng_key_pixel)
-    int32_t verify;    // PT_AMD_VERIFY_BOUNDS=1: re-run the plain closest-hit loop, count differences
-};
-struct TileDev {
-    int32_t W, rank, world, npix, spp, P, depth, iter_first;
-    uint64_t wdiv;   // ceil(2^40 / W) when npix * W < 2^40 (then lp / W == lp * wdiv >> 40), else 0
-};
+static_assert(offsetof(SceneDev, room) == 192 && sizeof(SceneDev) == 304, "kernarg bytes of the scene tables");
 struct KArgs {
     SceneDev S;
     CamDev cam;
@@ -363,18 +340,6 @@ struct PrivStack {
     __device__ void set(int i, int v) const { a[i] = v; }
 };
 
-// Child-pair layout of the same tree: one 64-byte entry per INTERIOR node holding both children's
-// boxes and codes, so deciding where to go from a node costs one fetch instead of one per child.
-//   code >= 0: interior child, entry index * 4 + its split axis;
-//   code <  0: leaf child, -(first triangle * 256 + triangle count) - 1.
-// The boxes tested, their outcomes (aabb_hit) and the near-first order are those of bvh_walk:
-// a child is tested at its parent instead of after being popped, and only passing children are
-// pushed, so the triangles tested, their order and the result are the same; used without the
-// bvh_cull extension and when the tree is shallow enough for the LDS stack (no overflow case).
-struct alignas(16) DPair {
-    v4f lmin, lmax, rmin, rmax;   // .w: left code (lmin.w), unused (lmax.w), right code (rmin.w), unused
-};
-
 template <class Stack>
 __device__ __forceinline__ MeshHit bvh_walk_pairs(const SceneDev& S, f3 o, f3 d, Stack stack) {
     MeshHit r{false, -1, -1, kFLT_MAX, 0.f, 0.f};
@@ -424,27 +389,6 @@ __device__ __forceinline__ MeshHit bvh_walk_pairs(const SceneDev& S, f3 o, f3 d,
     }
     return r;
 }
-
-// 4-wide layout (k_traverse4): the pair entry of interior node N with each interior child X
-// replaced by X's own two children when both boxes lie inside X's box (checked on the host, so a
-// grandchild box that the ray hits implies a hit on X's box — the slab test is monotone in the box
-// bounds for a finite ray: (b - o) * inv is nondecreasing in b for inv > 0 and nonincreasing for
-// inv < 0, so X's slab intervals contain the grandchild's).  The leaves reached, and in the
-// near-first order below the triangles tested, are BVHIntersectionTest's (intersections.cu:170-224).
-//   Slots 0-1: N's left child's group (X's two children, or the child itself in slot 0), slots 2-3
-// the right child's.  meta bits: valid slots (0-3) | N's axis << 4 | left group's axis << 6 |
-// right group's axis << 8 (3: a one-slot group, never swapped).  Codes as DPair's, with interior
-// codes = quad index.  Boxes are SoA (one v4f per bound and axis) so the four slab tests run two
-// slots per packed f32 instruction.
-// An interior code carries its quad's meta bits above the index (kQuadMetaShift), so a walk learns
-// the order of a quad's slots from the code that led to it and loads 112 of the entry's 128 bytes.
-struct alignas(16) DQuad {
-    v4f lox, hix, loy, hiy, loz, hiz;
-    v4f code;   // int bits
-    v4f meta;   // [0]: int bits (above; also in the interior codes that point here)
-};
-constexpr int kQuadMetaShift = 21;                        // interior code = quad index | meta << 21
-constexpr int kQuadIdxMask = (1 << kQuadMetaShift) - 1;   // (a layout of more quads is not built)
 
 constexpr int kRecWalkHere = -2;   // k_traverse4 record: not walked (non-finite ray), k_bounce walks it
 constexpr int kWalkDone = (int)0x80000000;   // k_traverse: no node left (below every leaf code, first < 2^23)
@@ -591,7 +535,6 @@ __device__ __forceinline__ Hit intersect_scene(const SceneDev& S, const FlagsDev
 // per ray instead of one per geom.  PT_AMD_VERIFY_BOUNDS=1 re-runs the plain loop and counts any
 // difference (pt_stats_t.bound_mismatch).
 
-constexpr int kLdsGeoms = 32;
 // What the exact tests and the hit normal read: 47 words, padded to a 52-word (208-byte) row so
 // the rows of up to 16 geoms start in distinct 4-bank windows — lanes of a wave testing different
 // geoms read without LDS bank conflicts (a 48-word row put rows r and r+4 on the same banks:
@@ -679,11 +622,11 @@ __device__ __forceinline__ uint32_t tag_bound(float v, uint32_t i) {
     return (b & ~31u) | i;
 }
 
-// The walls of a room (SceneDev::room_*, find_room) bounded as one group: per axis a the two plane
+// The walls of a room (SceneDev::room, find_room) bounded as one group: per axis a the two plane
 // parameters tL = (L_a - o_a) * r_a and tH = (H_a - o_a) * r_a in the packed operations of
 // bound_wbox_tagged (L_a: the -a wall's high plane, H_a: the +a wall's low plane, L_a < H_a), then
 //  - the wall AHEAD (+a when r_a's sign bit is clear, else -a) gets the tagged bound
-//    fma(max(tL, tH, 0), rlt, -room_wback), and
+//    fma(max(tL, tH, 0), rlt, -room.wback), and
 //  - the wall BEHIND is a miss when min(tL, tH) < 0, and otherwise a candidate with bound 0.
 // Three subtractions and three multiplications serve up to six walls, for any origin and direction.
 // The closest hit keeps its bits:
@@ -691,7 +634,7 @@ __device__ __forceinline__ uint32_t tag_bound(float v, uint32_t i) {
 //    with H_a < whi, so its min(tx.x, tx.y) is tx.x = (H_a - o_a) * r_a = tH bit for bit, whatever the
 //    origin, and tH >= tL (H_a > L_a, products round monotonically); likewise tL for r_a < 0.  So
 //    max(tL, tH, 0) <= the wall's E0 (when 0 * inf makes one of them NaN the maxNum chain drops it:
-//    smaller still), and with rlt > 0, room_wback >= the wall's wback and the fma rounding
+//    smaller still), and with rlt > 0, room.wback >= the wall's wback and the fma rounding
 //    monotonically the value is a lower bound no larger than the loop's.
 //  - The wall behind is called a miss only where bound_wbox_tagged calls it one: min(tL, tH) < 0 is
 //    that wall's facing plane with a negative parameter, its other plane lies further back, so its
@@ -699,7 +642,7 @@ __device__ __forceinline__ uint32_t tag_bound(float v, uint32_t i) {
 //    the wall's slab) claims nothing: bound 0.
 //  - The wall ahead is also a miss when the ray is past the walls' common box on another axis b
 //    before it reaches the wall's plane: qa_b < max(tL, tH, 0), qa_b = the larger parameter of the
-//    box's two b-planes (room_out).  Every wall's own widened b-extent lies within those planes, so its
+//    box's two b-planes (room.out).  Every wall's own widened b-extent lies within those planes, so its
 //    exit parameter on axis b is <= qa_b (same factor r_b, monotone), hence its X <= qa_b < E0:
 //    bound_wbox_tagged's miss.  This is what keeps a ray that leaves through an open face, or past a
 //    neighbouring wall, from being a candidate of every wall ahead (a NaN compares false: no claim).
@@ -718,7 +661,7 @@ __device__ __forceinline__ uint32_t tag_bound(float v, uint32_t i) {
 // stayed a candidate with bound 0: an exact test that always misses, run by the whole wave.  The wall
 // behind is therefore ALSO a miss when
 //        Lin_a < o_a  and  o_a < Hin_a        (two float comparisons, no arithmetic on the ray)
-// with the walls' TIGHT facing planes (room_in): Lin_a >= every a-coordinate of the -a wall's widened cube
+// with the walls' TIGHT facing planes (room.in): Lin_a >= every a-coordinate of the -a wall's widened cube
 // W (the image, under the exact inverse of the float matrix `inv`, of [slo, shi]), Hin_a <= those of the
 // +a wall's; for a face without a wall the infinity that leaves the other comparison alone.  The wall
 // behind is the -a wall when r_a's sign bit is clear and the +a wall when it is set, as above, so the
@@ -769,24 +712,24 @@ __device__ __forceinline__ void bound_room_tagged(const SceneDev& S, f3 o, f3 r,
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float oa = at(o, a), ra = at(r, a);
-        t[a] = ((v2f){S.room_pl[2 * a], S.room_pl[2 * a + 1]} - (v2f){oa, oa}) * (v2f){ra, ra};
-        const v2f q = ((v2f){S.room_out[2 * a], S.room_out[2 * a + 1]} - (v2f){oa, oa}) * (v2f){ra, ra};
+        t[a] = ((v2f){S.room.pl[2 * a], S.room.pl[2 * a + 1]} - (v2f){oa, oa}) * (v2f){ra, ra};
+        const v2f q = ((v2f){S.room.out[2 * a], S.room.out[2 * a + 1]} - (v2f){oa, oa}) * (v2f){ra, ra};
         ta[a] = fmaxf(fmaxf(t[a].x, t[a].y), 0.0f);
         qa[a] = fmaxf(q.x, q.y);
     }
     bool counted = false;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float v = fmaf(ta[a], rlt, -S.room_wback);
+        const float v = fmaf(ta[a], rlt, -S.room.wback);
         // the two tags by r_a's sign bit in bit operations (selects between two scalars would first
         // move both into vector registers): ahead = sign ? wl : wh, behind = the other
-        const uint32_t wl = S.room_tag[2 * a], wh = S.room_tag[2 * a + 1], wx = wl ^ wh;
+        const uint32_t wl = S.room.tag[2 * a], wh = S.room.tag[2 * a + 1], wx = wl ^ wh;
         const uint32_t neg = (uint32_t)((int32_t)__float_as_uint(at(r, a)) >> 31);
         const uint32_t ahead = (neg & wx) ^ wh;
         const bool past = fminf(qa[(a + 1) % 3], qa[(a + 2) % 3]) < ta[a];
         insert_tagged(tag_bound(v, 0u) | ahead | (past ? 0x7f800000u : 0u));
         const bool back = fminf(t[a].x, t[a].y) < 0.0f;
-        const bool left = at(o, a) > S.room_in[2 * a] && at(o, a) < S.room_in[2 * a + 1];
+        const bool left = at(o, a) > S.room.in[2 * a] && at(o, a) < S.room.in[2 * a + 1];
         if (COUNT) counted = counted || (left && !back && (ahead ^ wx) < 0x7f800000u);
         insert_tagged((back || left) ? 0x7f800000u : (ahead ^ wx));
     }
@@ -1024,12 +967,12 @@ __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsD
         auto insert = [&](float lo, int i) { insert_tagged(lo == kInf ? 0x7f800000u : tag_bound(lo, (uint32_t)i)); };
         const float rlt = rl * S.wb_tslack;
         int j3 = S.bk[3];
-        // the room's walls (the first room_n world-box cubes) as one group (bound_room_tagged).  Later
+        // the room's walls (the first room.n world-box cubes) as one group (bound_room_tagged).  Later
         // bounces only: their gmask is all ones, the camera rays keep their masks and the loop.
-        const bool room = SEL && gmask == ~0u && S.room_n > 0;
+        const bool room = SEL && gmask == ~0u && S.room.n > 0;
         if (room) {
             bound_room_tagged<COUNT>(S, ro, invd, rlt, insert_tagged, COUNT && cnt ? &cnt->room_depart : nullptr);
-            j3 += S.room_n;
+            j3 += S.room.n;
         }
         for (int j = j3; j < S.bk[4]; ++j)   // world-box cubes: packed slabs
             if ((gmask >> B[j].orig) & 1u) insert_tagged(bound_wbox_tagged(B[j], ro, invd, rlt, (uint32_t)B[j].orig));
@@ -1093,7 +1036,7 @@ __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsD
             if (room) {   // the room's walls as the pass above takes them
                 auto ins2t = [&](uint32_t t) { ins2(t >= 0x7f800000u ? kInf : __uint_as_float(t), (int)(t & 31u)); };
                 bound_room_tagged(S, r2, invd, rlt, ins2t);
-                k3 += S.room_n;
+                k3 += S.room.n;
             }
             for (int j = k3; j < S.bk[4]; ++j)
                 if ((gmask >> B[j].orig) & 1u) ins2(bound_geom<3, SEL>(B[j], r2, rd, invd, rl, rinf), B[j].orig);
@@ -3398,13 +3341,11 @@ struct pt_ctx {
     std::vector<ProfEv> events;   // pool; the first `ev_used` are recorded and unread
     size_t ev_used = 0;
     size_t path_cap = 0;          // entries per path buffer (>= P, see pt_create)
-    std::vector<DGeom> hgeoms;    // host copy of the geom table (bounds re-derived by pt_set_flags)
-    std::vector<float> wtight;    // bkind 3: the widened cube's world hull before the pad, rounded outward,
-                                  // (lo, hi) of axis r at [6 * geom + 2 * r] (update_bounds; find_room's room_in)
+    pt::BoundsHost bounds;        // host copy of the geom table and what its bounds derive from (pt_bounds.cpp;
+                                  // re-derived by pt_set_flags, copied into args.S by sync_bounds)
     uint32_t* d_cmask = nullptr;  // first-bounce geom masks, one per 64 tile pixels (build_cmask)
     DGeom* d_geoms = nullptr;
     DGeom* d_bgeoms = nullptr;    // the same geoms ordered by bound kind (SceneDev::bgeoms)
-    double scene_ext = 0.0;       // max |coordinate| over every surface and the camera position
     // Batched passes (spp > 1): pass p's path colours go to colbuf half h = p & 1 and are added
     // into the image by k_finalize_spp on fin_stream, concurrently with the next pass's bounces
     // on the caller's stream (memory-bound finalize beside the VALU-bound first bounce).  A pass
@@ -3568,322 +3509,18 @@ void set_flags_dev(pt_ctx* c, const pt_flags& f) {
     c->args.fl.verify = vb && std::strcmp(vb, "1") == 0;
 }
 
-float bits_to_float(int32_t v) {
-    float f;
-    std::memcpy(&f, &v, 4);
-    return f;
-}
-int32_t __float_as_int_host(float f) {
-    int32_t v;
-    std::memcpy(&v, &f, 4);
-    return v;
+using pt::bits_to_float;
+using pt::__float_as_int_host;
+
+// The widened bounds (pt::update_bounds) as the kernels read them: the scalars and the room of
+// c->bounds into the launch arguments.  The geom rows are uploaded by the callers.
+void sync_bounds(pt_ctx* c) {
+    c->args.S.abs_slack = c->bounds.abs_slack;
+    c->args.S.wb_tslack = c->bounds.wb_tslack;
+    c->args.S.room = c->bounds.room;
 }
 
-Affine to_affine(const float* m) {   // glm column-major 4x4 -> 3x4 + the exact w=0 terms
-    Affine a;
-    for (int col = 0; col < 4; ++col)
-        for (int r = 0; r < 3; ++r) a.c[col][r] = m[4 * col + r];
-    for (int r = 0; r < 3; ++r) a.z3[r] = m[12 + r] * 0.0f;
-    return a;
-}
-
-// The room of bound_room_tagged: at most one world-box cube (bkind 3) per face -x, +x, -y, +y, -z, +z
-// and the box B between the widened planes with which those walls face each other — H_a the low plane
-// of the +a wall, L_a the high plane of the -a wall, +-inf for a face without a wall.
-//   Per face the candidate is the cube that lies wholly on that side of the centre of the world-box
-// cubes' common box and has the largest cross-section there (a cube serves one face only).  A wall
-// stays only if its extent on the other two axes covers B's, B ending on an open face where the box
-// of the remaining walls ends (their unwidened boxes, which every widened wall of the same extent
-// covers); a wall that does not cover its face would send the rays leaving past it through extra
-// exact tests — slower, never wrong, since bound_room_tagged's bounds hold for any wall.  The room
-// needs three walls (L_a < H_a follows from the selection).  Tags carry five bits, as in the pass
-// itself.  PT_AMD_ROOM=0 leaves the walls in the per-cube loop (A/B and tests; the same bits).
-void find_room(pt_ctx* c) {
-    SceneDev& S = c->args.S;
-    S.room_n = 0;
-    S.room_wback = 0.0f;
-    for (int f = 0; f < 6; ++f) {
-        S.room_pl[f] = (f & 1) ? HUGE_VALF : -HUGE_VALF;
-        S.room_out[f] = (f & 1) ? -HUGE_VALF : HUGE_VALF;
-        S.room_tag[f] = 0x7f800000u;
-        S.room_in[f] = (f & 1) ? -HUGE_VALF : HUGE_VALF;   // no origin is between these: no claim
-    }
-    const std::vector<DGeom>& G = c->hgeoms;
-    const size_t n = G.size();
-    if (n > (size_t)kLdsGeoms) return;
-    if (const char* e = std::getenv("PT_AMD_ROOM"))
-        if (std::atoi(e) == 0) return;
-    // the cubes' own (unwidened) world boxes
-    std::vector<double> elo(3 * n, HUGE_VAL), ehi(3 * n, -HUGE_VAL);
-    double alo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, ahi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    for (size_t i = 0; i < n; ++i) {
-        if (G[i].bkind != 3) continue;
-        for (int corner = 0; corner < 8; ++corner)
-            for (int r = 0; r < 3; ++r) {
-                double v = G[i].xf.c[3][r];
-                for (int k = 0; k < 3; ++k) v += (double)G[i].xf.c[k][r] * ((corner >> k) & 1 ? 0.5 : -0.5);
-                elo[3 * i + r] = std::min(elo[3 * i + r], v);
-                ehi[3 * i + r] = std::max(ehi[3 * i + r], v);
-            }
-        for (int r = 0; r < 3; ++r) {
-            alo[r] = std::min(alo[r], elo[3 * i + r]);
-            ahi[r] = std::max(ahi[r], ehi[3 * i + r]);
-        }
-    }
-    int face[6];
-    std::vector<char> used(n, 0);
-    for (int f = 0; f < 6; ++f) {
-        const int a = f >> 1, b = (a + 1) % 3, e = (a + 2) % 3;
-        const double mid = 0.5 * (alo[a] + ahi[a]);
-        double area = -1.0;
-        face[f] = -1;
-        for (size_t i = 0; i < n; ++i) {
-            if (G[i].bkind != 3 || used[i]) continue;
-            if (!((f & 1) ? (double)G[i].wlo[a] > mid : (double)G[i].whi[a] < mid)) continue;
-            const double ar = ((double)G[i].whi[b] - (double)G[i].wlo[b]) * ((double)G[i].whi[e] - (double)G[i].wlo[e]);
-            if (ar > area) { area = ar; face[f] = (int)i; }
-        }
-        if (face[f] >= 0) used[(size_t)face[f]] = 1;
-    }
-    float pl[6];
-    for (;;) {
-        double blo[3], bhi[3];   // B, ended on its open faces
-        int walls = 0;
-        for (int a = 0; a < 3; ++a) {
-            double wl = HUGE_VAL, wh = -HUGE_VAL;
-            for (int f = 0; f < 6; ++f)
-                if (face[f] >= 0) {
-                    wl = std::min(wl, elo[3 * (size_t)face[f] + a]);
-                    wh = std::max(wh, ehi[3 * (size_t)face[f] + a]);
-                    walls += a == 0;
-                }
-            pl[2 * a] = face[2 * a] >= 0 ? G[(size_t)face[2 * a]].whi[a] : -HUGE_VALF;
-            pl[2 * a + 1] = face[2 * a + 1] >= 0 ? G[(size_t)face[2 * a + 1]].wlo[a] : HUGE_VALF;
-            blo[a] = face[2 * a] >= 0 ? (double)pl[2 * a] : wl;
-            bhi[a] = face[2 * a + 1] >= 0 ? (double)pl[2 * a + 1] : wh;
-        }
-        if (walls < 3) return;
-        bool dropped = false;
-        for (int f = 0; f < 6; ++f) {
-            if (face[f] < 0) continue;
-            const DGeom& d = G[(size_t)face[f]];
-            for (int k = 1; k < 3; ++k) {
-                const int b = ((f >> 1) + k) % 3;
-                if (!((double)d.wlo[b] <= blo[b] && (double)d.whi[b] >= bhi[b])) { face[f] = -1; dropped = true; break; }
-            }
-        }
-        if (!dropped) break;
-    }
-    // (L_a < H_a needs no test: a -a wall's high plane is below the centre, a +a wall's low plane above)
-    for (int f = 0; f < 6; ++f) {
-        S.room_pl[f] = pl[f];
-        if (face[f] < 0) continue;
-        S.room_tag[f] = (uint32_t)face[f];
-        S.room_wback = std::max(S.room_wback, G[(size_t)face[f]].wback);
-        for (int a = 0; a < 3; ++a) {
-            S.room_out[2 * a] = std::min(S.room_out[2 * a], G[(size_t)face[f]].wlo[a]);
-            S.room_out[2 * a + 1] = std::max(S.room_out[2 * a + 1], G[(size_t)face[f]].whi[a]);
-        }
-        ++S.room_n;
-    }
-    // The tight facing planes of bound_room_tagged's departure claim: a wall's own hull plane, and for a
-    // face without a wall the infinity that leaves the claim to the other face's plane alone (what is
-    // claimed a miss there is the missing wall, which is no candidate anyway).  PT_AMD_ROOM_DEPART=0
-    // keeps the values no origin lies between (A/B and tests; the same bits).
-    bool depart = S.room_n > 0;
-    if (const char* e = std::getenv("PT_AMD_ROOM_DEPART"))
-        if (std::atoi(e) == 0) depart = false;
-    for (int f = 0; f < 6 && depart; ++f)
-        S.room_in[f] = face[f] >= 0 ? c->wtight[6 * (size_t)face[f] + 2 * (size_t)(f >> 1) + (size_t)(~f & 1)]
-                                    : ((f & 1) ? HUGE_VALF : -HUGE_VALF);
-}
-
-// Widened bounds of the bounded closest-hit pass (bound_geom), sized from R = the largest
-// |coordinate| any ray origin can have: a surface point (+1e-4 offsets) or the camera lens.
-//   qo = inv * ro is computed with <= 4 ulp of S_a = sum_i |inv_ia| R + |inv_3a| absolute error by
-// either side (exact test, bounds test), the exact slab parameters add <= 5 ulp of (S_a + 0.5):
-// mu_a = 2^-18 (S_a + 1) is >= 10x that.  The sphere's b^2 - a c cancels to <= 2^-20 (S + 1)^2:
-// kappa = 2^-16 (S + 1)^2.  tslack covers the back-transform (transform * inverse != I in float)
-// and the rounding of the reference's length(); abs_slack its absolute part.
-void update_bounds(pt_ctx* c, float aperture) {
-    const double R = c->scene_ext + std::fabs((double)aperture) + 1e-2;
-    c->wtight.assign(6 * c->hgeoms.size(), 0.0f);
-    for (DGeom& d : c->hgeoms) {
-        double smax = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            double S = std::fabs((double)d.inv.c[3][a]);
-            for (int i = 0; i < 3; ++i) S += std::fabs((double)d.inv.c[i][a]) * R;
-            const double mu = std::ldexp(S + 1.0, -18);
-            d.slo[a] = (float)(-0.5 - mu);
-            d.shi[a] = (float)(0.5 + mu);
-            smax = std::max(smax, S);
-        }
-        d.r2w = (float)(0.25 + std::ldexp((smax + 1.0) * (smax + 1.0), -16));
-        // departing-ray test: |qo_exact - qo_bound| <= 2^-21 S_ray (S_ray <= cs |ro|_inf + c3) moves
-        // |qo|^2 by <= 2^-20 |qo| S_ray; the dot products add <= 2^-21 |qo|^2.  kappa_ray is >= 6x that.
-        double cs = 0.0, c3 = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            cs = std::max(cs, std::fabs((double)d.inv.c[0][a]) + std::fabs((double)d.inv.c[1][a]) +
-                                  std::fabs((double)d.inv.c[2][a]));
-            c3 = std::max(c3, std::fabs((double)d.inv.c[3][a]));
-        }
-        d.kcs = (float)std::ldexp(cs, -18);
-        d.kc3 = (float)std::ldexp(c3 + 2.0, -18);
-        d.bkind = d.type == PT_GEOM_CUBE ? 1 : (d.type == PT_GEOM_SPHERE ? 2 : 0);
-        if (d.type == PT_GEOM_SPHERE) {
-            // uniform scale (x rotation): G = L^T L = sigma^2 I up to delta, L = the linear part of inv
-            double G[3][3], tr = 0.0, dev = 0.0;
-            for (int i = 0; i < 3; ++i)
-                for (int j = 0; j < 3; ++j) {
-                    G[i][j] = 0.0;
-                    for (int a = 0; a < 3; ++a) G[i][j] += (double)d.inv.c[i][a] * (double)d.inv.c[j][a];
-                }
-            for (int i = 0; i < 3; ++i) tr += G[i][i];
-            const double s2 = tr / 3.0;
-            for (int i = 0; i < 3; ++i)
-                for (int j = 0; j < 3; ++j) dev = std::max(dev, std::fabs(G[i][j] - (i == j ? s2 : 0.0)));
-            if (s2 > 0.0 && dev <= std::ldexp(s2, -20)) {
-                // the world-space dot products differ from the object-space ones by the
-                // non-uniformity (<= 2^-20 relative) and the rounding of w = ro - centre (within the
-                // 4 ulp of S_a assumed above): margins doubled
-                for (int k = 0; k < 3; ++k) d.wlo[k] = d.xf.c[3][k];
-                d.whi[0] = (float)s2;
-                // bound_sphere_tagged's per-geom constants: 1 / is2 and the pull-back factor
-                // 1.0002e-4 / sqrt(is2), rounded up (is2 as the device reads it, a float)
-                d.whi[1] = (float)(1.0 / (double)d.whi[0]);
-                d.back = std::nextafter((float)(1.0002e-4 / std::sqrt((double)d.whi[0])), HUGE_VALF);
-                d.r2w = (float)(0.25 + std::ldexp((smax + 1.0) * (smax + 1.0), -15));
-                d.kcs *= 2.0f;
-                d.kc3 *= 2.0f;
-                d.bkind = 4;
-            }
-        }
-        if (d.type == PT_GEOM_CUBE) {   // world box of the widened cube, if the transform is axis-aligned
-            double M[3][3], X[3][3];
-            for (int r = 0; r < 3; ++r)
-                for (int k = 0; k < 3; ++k) M[r][k] = d.inv.c[k][r];   // q = M p + t
-            const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) -
-                               M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
-                               M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-            bool aligned = std::fabs(det) > 0.0;
-            if (aligned) {
-                for (int r = 0; r < 3; ++r)
-                    for (int k = 0; k < 3; ++k) {
-                        const int r1 = (k + 1) % 3, r2 = (k + 2) % 3, k1 = (r + 1) % 3, k2 = (r + 2) % 3;
-                        X[r][k] = (M[r1][k1] * M[r2][k2] - M[r1][k2] * M[r2][k1]) / det;   // adjugate / det
-                    }
-                for (int r = 0; r < 3 && aligned; ++r) {
-                    double big = 0.0;
-                    for (int k = 0; k < 3; ++k) big = std::max(big, std::fabs(X[r][k]));
-                    int n = 0;
-                    // (1e-4 of the row's axis: a 90-degree rotation in float has cos = -4.4e-8, which next
-                    // to a 0.01 : 10 scale — the Cornell ceiling and back wall — is 4.4e-5 of the thin axis;
-                    // the world box grows by that share of the slab.  Only tightness depends on this bound:
-                    // the world box below holds the widened cube at any rotation, and `back` takes the
-                    // transform's norm.)
-                    for (int k = 0; k < 3; ++k) n += std::fabs(X[r][k]) > 1e-4 * big;
-                    aligned = n == 1;
-                }
-            }
-            if (aligned) {
-                double stretch = 0.0, lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-                for (int corner = 0; corner < 8; ++corner) {
-                    double q[3];
-                    for (int k = 0; k < 3; ++k) q[k] = ((corner >> k) & 1 ? d.shi[k] : d.slo[k]) - d.inv.c[3][k];
-                    for (int r = 0; r < 3; ++r) {
-                        const double v = X[r][0] * q[0] + X[r][1] * q[1] + X[r][2] * q[2];
-                        lo[r] = std::min(lo[r], v);
-                        hi[r] = std::max(hi[r], v);
-                    }
-                }
-                // the largest stretch ||X||_2 <= sqrt(||X||_1 ||X||_inf): the largest entry when X has one
-                // entry per row, and still a bound with the small others the test above lets through
-                double n1 = 0.0, ninf = 0.0;
-                for (int r = 0; r < 3; ++r) {
-                    ninf = std::max(ninf, std::fabs(X[r][0]) + std::fabs(X[r][1]) + std::fabs(X[r][2]));
-                    n1 = std::max(n1, std::fabs(X[0][r]) + std::fabs(X[1][r]) + std::fabs(X[2][r]));
-                    for (int k = 0; k < 3; ++k) stretch = std::max(stretch, std::fabs(X[r][k]));
-                }
-                stretch = std::max(stretch, std::sqrt(n1 * ninf));
-                const double pad = std::ldexp(R + 1.0, -18);
-                for (int r = 0; r < 3; ++r) {
-                    d.wlo[r] = (float)(lo[r] - pad - std::ldexp(std::fabs(lo[r]), -18));
-                    d.whi[r] = (float)(hi[r] + pad + std::ldexp(std::fabs(hi[r]), -18));
-                    // the hull itself, for the departure claim of bound_room_tagged: moved out by 2^-40 (R + 1)
-                    // (the rounding of X and of the sums above is a few 2^-53 of the coordinates, also where
-                    // the plane itself cancels to nearly 0), then one float further out than the nearest one
-                    const double eps = std::ldexp(R + 1.0, -40);
-                    float* tg = &c->wtight[6 * (size_t)(&d - c->hgeoms.data()) + 2 * (size_t)r];
-                    tg[0] = std::nextafter((float)(lo[r] - eps), -HUGE_VALF);
-                    tg[1] = std::nextafter((float)(hi[r] + eps), HUGE_VALF);
-                }
-                d.back = (float)(1.0002e-4 * stretch * (1.0 + 1e-5));
-                for (int r = 0; r < 3; ++r) {
-                    d.wbox[2 * r] = d.wlo[r];
-                    d.wbox[2 * r + 1] = d.whi[r];
-                }
-                d.bkind = 3;
-            } else {
-                // oriented cube (bkind 1): bound_obox_tagged's pull-back factor, 1.0002e-4 / sigma_min(L)
-                // bounded by the Frobenius norm of X = L^-1 (a singular L: +inf, the bound is then 0)
-                double fro = HUGE_VAL;
-                if (std::fabs(det) > 0.0) {   // (X is computed above exactly then)
-                    fro = 0.0;
-                    for (int r = 0; r < 3; ++r)
-                        for (int k = 0; k < 3; ++k) fro += X[r][k] * X[r][k];
-                }
-                d.back = std::isfinite(fro) ? std::nextafter((float)(1.0002e-4 * std::sqrt(fro) * (1.0 + 1e-5)), HUGE_VALF)
-                                            : HUGE_VALF;
-            }
-        }
-        double dev = 0.0;   // Frobenius norm of xf_lin * inv_lin - I
-        for (int r = 0; r < 3; ++r)
-            for (int col = 0; col < 3; ++col) {
-                double m = 0.0;
-                for (int k = 0; k < 3; ++k) m += (double)d.xf.c[k][r] * (double)d.inv.c[col][k];
-                m -= r == col ? 1.0 : 0.0;
-                dev += m * m;
-            }
-        d.tslack = (float)(1.0 - 4.0 * std::sqrt(dev) - std::ldexp(1.0, -14));
-    }
-    c->args.S.abs_slack = (float)std::ldexp(R + 1.0, -17);
-    // bound_wbox_tagged: one tslack for every world-box cube (their smallest), folded into the pull-back
-    float ts = 1.0f;
-    for (const DGeom& d : c->hgeoms)
-        if (d.bkind == 3) ts = std::min(ts, d.tslack);
-    c->args.S.wb_tslack = ts;
-    for (DGeom& d : c->hgeoms)
-        d.wback = d.bkind == 3 ? std::nextafter((float)((double)d.back * (double)ts), HUGE_VALF) : 0.0f;
-    find_room(c);
-}
-
-// ---- first-bounce geom masks ----------------------------------------------------------------
-// A wave of the first bounce traces 64 consecutive tile pixels of one iteration.  Every camera
-// ray of those pixels (any SSAA jitter in [0, 1) pixel, any lens sample within the aperture) is
-//   o + s (F - o), s >= 0,   o in cam.pos + [-a, a]^2 x {0},   F in the focal-plane image of the
-// pixels' rectangle (DoF; raygen's focus point, pathtrace.cu:203-224), or
-//   cam.pos + s v,           v in the span of the rectangle's view vectors (no DoF).
-// Bounding o and F - o (or v) by boxes and asking, axis by axis, for a common s >= 0 at which the
-// ray box meets a geom's world box gives a conservative "can hit" test (never false for a ray that
-// hits).  The geom's box is its test region [slo, shi]^3 (already wider than the exact test's
-// rounding, update_bounds) mapped by the exact inverse of `inv`, padded again.  A geom outside the
-// mask is skipped by the bounds pass of those rays: the closest hit is unchanged (intersect_bounded).
-static bool beam_meets_box(const double olo[3], const double ohi[3], const double dlo[3], const double dhi[3],
-                           const double blo[3], const double bhi[3]) {
-    double smin = 0.0, smax = HUGE_VAL;
-    for (int k = 0; k < 3; ++k) {
-        // o_lo + s d_lo <= b_hi  and  o_hi + s d_hi >= b_lo  (the ray box's extent along axis k at s)
-        const double c1 = bhi[k] - olo[k], c2 = blo[k] - ohi[k];
-        if (dlo[k] > 0.0) smax = std::min(smax, c1 / dlo[k]);
-        else if (dlo[k] < 0.0) smin = std::max(smin, c1 / dlo[k]);
-        else if (c1 < 0.0) return false;
-        if (dhi[k] > 0.0) smin = std::max(smin, c2 / dhi[k]);
-        else if (dhi[k] < 0.0) smax = std::min(smax, c2 / dhi[k]);
-        else if (c2 > 0.0) return false;
-    }
-    return smin <= smax * (1.0 + 1e-9) + 1e-12;
-}
-
+// First-bounce geom masks (pt::camera_masks), one word per 64 tile pixels.
 int build_cmask(pt_ctx* c) {
     KArgs& A = c->args;
     A.cmask = nullptr;
@@ -3893,116 +3530,11 @@ int build_cmask(pt_ctx* c) {
     const int ng = A.S.ngeoms;
     const char* off = std::getenv("PT_AMD_NO_CMASK");
     if ((off && std::strcmp(off, "1") == 0) || ng <= 0 || ng > kLdsGeoms || A.S.ntris > 0) return PT_OK;
-    const TileDev& T = A.tile;
-    const CamDev& cam = A.cam;
-    const size_t nblk = ((size_t)T.npix + 63) / 64;
+    const size_t nblk = ((size_t)A.tile.npix + 63) / 64;
     if (!c->d_cmask)
         if (int rc = c->alloc(&c->d_cmask, nblk)) return rc;
-    // world boxes of the geoms' test regions
-    std::vector<std::array<double, 6>> gb((size_t)ng);
-    std::vector<bool> always((size_t)ng, false);
-    for (int g = 0; g < ng; ++g) {
-        const DGeom& d = c->hgeoms[(size_t)g];
-        if (d.type != PT_GEOM_CUBE && d.type != PT_GEOM_SPHERE) { always[(size_t)g] = true; continue; }
-        double M[3][3], X[3][3];
-        for (int r = 0; r < 3; ++r)
-            for (int k = 0; k < 3; ++k) M[r][k] = d.inv.c[k][r];   // q = M p + t
-        const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) -
-                           M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
-                           M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-        if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) { always[(size_t)g] = true; continue; }
-        for (int r = 0; r < 3; ++r)
-            for (int k = 0; k < 3; ++k) {
-                const int r1 = (k + 1) % 3, r2 = (k + 2) % 3, k1 = (r + 1) % 3, k2 = (r + 2) % 3;
-                X[r][k] = (M[r1][k1] * M[r2][k2] - M[r1][k2] * M[r2][k1]) / det;
-            }
-        const double rs = d.type == PT_GEOM_SPHERE ? std::sqrt(std::max(0.0, (double)d.r2w)) : 0.0;
-        double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-        for (int corner = 0; corner < 8; ++corner) {
-            double q[3];
-            for (int k = 0; k < 3; ++k) {
-                const double a = std::min((double)d.slo[k], -rs), b = std::max((double)d.shi[k], rs);
-                q[k] = ((corner >> k) & 1 ? b : a) * (1.0 + 1e-4) - d.inv.c[3][k];
-            }
-            for (int r = 0; r < 3; ++r) {
-                const double v = X[r][0] * q[0] + X[r][1] * q[1] + X[r][2] * q[2];
-                lo[r] = std::min(lo[r], v);
-                hi[r] = std::max(hi[r], v);
-            }
-        }
-        for (int r = 0; r < 3; ++r) {
-            const double pad = 1e-3 + 1e-5 * std::max(std::fabs(lo[r]), std::fabs(hi[r]));
-            gb[(size_t)g][r] = lo[r] - pad;
-            gb[(size_t)g][3 + r] = hi[r] + pad;
-        }
-        if (!std::isfinite(gb[(size_t)g][0] + gb[(size_t)g][1] + gb[(size_t)g][2] + gb[(size_t)g][3] +
-                           gb[(size_t)g][4] + gb[(size_t)g][5]))
-            always[(size_t)g] = true;
-    }
-    const double pos[3] = {cam.pos[0], cam.pos[1], cam.pos[2]};
-    const double jit = A.fl.ssaa ? 1.0 : 0.0, eps = 0.01;   // pixel units
-    const bool dof = A.fl.dof != 0;
-    const double ap = std::fabs((double)A.fl.aperture), focal = A.fl.focal;
-    // rays of tile row `row`, tile columns [x0, x1]: their geoms
-    auto row_mask = [&](int row, int x0, int x1) -> uint32_t {
-        const int y = row * T.world + T.rank;
-        const double ax0 = x0 - cam.res[0] * 0.5 - eps, ax1 = x1 - cam.res[0] * 0.5 + jit + eps;
-        const double ay0 = y - cam.res[1] * 0.5 - eps, ay1 = y - cam.res[1] * 0.5 + jit + eps;
-        double v[4][3];
-        for (int q = 0; q < 4; ++q) {
-            const double ax = q & 1 ? ax1 : ax0, ay = q & 2 ? ay1 : ay0;
-            for (int k = 0; k < 3; ++k)
-                v[q][k] = (double)cam.view[k] - (double)cam.right[k] * cam.pl[0] * ax - (double)cam.up[k] * cam.pl[1] * ay;
-        }
-        double olo[3], ohi[3], dlo[3], dhi[3];
-        if (!dof) {
-            for (int k = 0; k < 3; ++k) {
-                olo[k] = pos[k] - 1e-4 * (1.0 + std::fabs(pos[k]));
-                ohi[k] = pos[k] + 1e-4 * (1.0 + std::fabs(pos[k]));
-                dlo[k] = std::min({v[0][k], v[1][k], v[2][k], v[3][k]});
-                dhi[k] = std::max({v[0][k], v[1][k], v[2][k], v[3][k]});
-                const double m = 1e-5 * (std::fabs(dlo[k]) + std::fabs(dhi[k]) + 1e-3);
-                dlo[k] -= m;
-                dhi[k] += m;
-            }
-        } else {
-            double flo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, fhi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-            int sign = 0;
-            for (int q = 0; q < 4; ++q) {
-                const double n = std::sqrt(v[q][0] * v[q][0] + v[q][1] * v[q][1] + v[q][2] * v[q][2]);
-                const int sg = v[q][2] > 0.0 ? 1 : -1;
-                if (!(std::fabs(v[q][2]) > 1e-3 * n) || (sign != 0 && sg != sign)) return ~0u;   // focus plane unbounded
-                sign = sg;
-                for (int k = 0; k < 3; ++k) {
-                    const double f = pos[k] + focal * v[q][k] / std::fabs(v[q][2]);
-                    flo[k] = std::min(flo[k], f);
-                    fhi[k] = std::max(fhi[k], f);
-                }
-            }
-            for (int k = 0; k < 3; ++k) {
-                const double fp = 1e-4 * (1.0 + std::fabs(flo[k]) + std::fabs(fhi[k]));
-                const double a = k < 2 ? ap * (1.0 + 1e-4) + 1e-6 : 1e-6;
-                olo[k] = pos[k] - a - 1e-4 * (1.0 + std::fabs(pos[k]));
-                ohi[k] = pos[k] + a + 1e-4 * (1.0 + std::fabs(pos[k]));
-                dlo[k] = (flo[k] - fp) - ohi[k];
-                dhi[k] = (fhi[k] + fp) - olo[k];
-            }
-        }
-        uint32_t m = 0u;
-        for (int g = 0; g < ng; ++g)
-            if (always[(size_t)g] || beam_meets_box(olo, ohi, dlo, dhi, &gb[(size_t)g][0], &gb[(size_t)g][3]))
-                m |= 1u << g;
-        return m;
-    };
-    std::vector<uint32_t> mask(nblk, 0u);
-    for (size_t b = 0; b < nblk; ++b) {
-        const int lp0 = (int)(b * 64), lp1 = std::min(T.npix - 1, lp0 + 63);
-        const int r0 = lp0 / T.W, r1 = lp1 / T.W;
-        uint32_t m = 0u;
-        for (int r = r0; r <= r1; ++r)
-            m |= row_mask(r, r == r0 ? lp0 - r * T.W : 0, r == r1 ? lp1 - r * T.W : T.W - 1);
-        mask[b] = m;
-    }
+    std::vector<uint32_t> mask;
+    pt::camera_masks(c->bounds, A.cam, A.fl, A.tile, mask);
     if (const char* st = std::getenv("PT_AMD_CMASK_STATS")) {
         if (std::strcmp(st, "1") == 0) {
             double tot = 0.0;
@@ -4171,228 +3703,11 @@ int launch_bounce(pt_ctx* c, bool first, bool spp1, int mesh, hipStream_t st, co
     return prof_end(ev, st);
 }
 
-// The 4-wide layout (DQuad) of the flattened tree `nodes` (DNode encoding: left child = i + 1).
-// An interior child X of a quad's node is replaced by its two children when both boxes lie inside
-// X's box as floats (the nesting k_traverse4's exactness rests on); otherwise it keeps one slot.
-// Also bounds the walk's stack: per quad (valid slots - 1) pushes, summed along the worst path.
-// Leaves of zero triangles (never built by the SAH builder) or a bound beyond the stack's capacity
-// leave the quad layout off (k_traverse's pair walk runs instead).
-// The flattened reference tree (BVH_tree.h:54-61) in the device encoding (DNode).
-std::vector<DNode> to_dnodes(const std::vector<pt_bvh_node>& bvh) {
-    std::vector<DNode> nodes(bvh.size());
-    for (size_t i = 0; i < bvh.size(); ++i) {
-        const pt_bvh_node& b = bvh[i];
-        const int32_t meta = b.sub_areas > 0 ? b.sub_areas : -(b.axis + 1);
-        const int32_t link = b.sub_areas > 0 ? b.first_area_idx : b.rchild_idx;
-        for (int k = 0; k < 3; ++k) { nodes[i].lo[k] = b.bmin[k]; nodes[i].hi[k] = b.bmax[k]; }
-        nodes[i].lo[3] = bits_to_float(meta);
-        nodes[i].hi[3] = bits_to_float(link);
-    }
-    return nodes;
-}
-
-// Host part: fills `quads`, the root's code and the stack bound; false = no quad layout.
-bool make_quads(const std::vector<DNode>& nodes, std::vector<DQuad>& quads, int32_t& root_code, int32_t& root_occ,
-                std::vector<int32_t>* slot_node = nullptr) {
-    const size_t n = nodes.size();
-    quads.clear();
-    if (slot_node) slot_node->clear();
-    if (n == 0) return false;
-    auto meta = [&](size_t i) { return __float_as_int_host(nodes[i].lo[3]); };
-    auto link = [&](size_t i) { return __float_as_int_host(nodes[i].hi[3]); };
-    for (size_t i = 0; i < n; ++i)
-        if (meta(i) == 0 || (meta(i) < 0 && (link(i) <= (int32_t)i + 1 || (size_t)link(i) >= n)))
-            return false;   // (a zero-triangle leaf is indistinguishable here; malformed links)
-    auto inside = [&](size_t in, size_t out) {
-        for (int k = 0; k < 3; ++k)
-            if (!(nodes[in].lo[k] >= nodes[out].lo[k] && nodes[in].hi[k] <= nodes[out].hi[k])) return false;
-        return true;
-    };
-    std::vector<int32_t> occ;   // stack bound of the walk below each quad
-    std::vector<int32_t> qid(n, -1);
-    auto leaf_code = [&](size_t i) { return -(link(i) * 256 + meta(i)) - 1; };
-    // first pass: assign quad ids in DFS order
-    std::vector<size_t> order;
-    {
-        std::vector<size_t> stk{0};
-        if (meta(0) > 0) stk.clear();
-        while (!stk.empty()) {
-            const size_t i = stk.back();
-            stk.pop_back();
-            qid[i] = (int32_t)order.size();
-            order.push_back(i);
-            const size_t ch[2] = {i + 1, (size_t)link(i)};
-            std::vector<size_t> kids;
-            for (size_t x : ch) {
-                if (meta(x) > 0) continue;
-                const size_t g[2] = {x + 1, (size_t)link(x)};
-                if (inside(g[0], x) && inside(g[1], x)) {
-                    for (size_t y : g)
-                        if (meta(y) <= 0) kids.push_back(y);
-                } else {
-                    kids.push_back(x);
-                }
-            }
-            for (auto it = kids.rbegin(); it != kids.rend(); ++it) stk.push_back(*it);
-        }
-    }
-    if (order.size() > (size_t)kQuadIdxMask) return false;
-    quads.resize(std::max<size_t>(order.size(), 1));
-    if (slot_node) slot_node->assign(4 * quads.size(), -1);
-    occ.assign(order.size(), 0);
-    // each quad's meta first: the interior codes pointing at a quad carry it
-    std::vector<uint32_t> qmeta(order.size(), 0);
-    for (size_t qi = 0; qi < order.size(); ++qi) {
-        const size_t i = order[qi];
-        uint32_t valid = 0, axes[2] = {3u, 3u};
-        const size_t ch[2] = {i + 1, (size_t)link(i)};
-        for (int g = 0; g < 2; ++g) {
-            const size_t x = ch[g];
-            if (meta(x) <= 0 && inside(x + 1, x) && inside((size_t)link(x), x)) {
-                valid |= 3u << (2 * g);
-                axes[g] = (uint32_t)(-meta(x) - 1);
-            } else {
-                valid |= 1u << (2 * g);
-            }
-        }
-        qmeta[qi] = valid | ((uint32_t)(-meta(i) - 1) << 4) | (axes[0] << 6) | (axes[1] << 8);
-    }
-    auto qcode = [&](size_t y) { return (int32_t)((uint32_t)qid[y] | (qmeta[(size_t)qid[y]] << kQuadMetaShift)); };
-    for (size_t qi = 0; qi < order.size(); ++qi) {
-        const size_t i = order[qi];
-        DQuad& Q = quads[qi];
-        std::memset(&Q, 0, sizeof Q);
-        uint32_t valid = 0, axes[2] = {3u, 3u};
-        int32_t codes[4] = {0, 0, 0, 0};
-        size_t box[4] = {0, 0, 0, 0};
-        const size_t ch[2] = {i + 1, (size_t)link(i)};
-        for (int g = 0; g < 2; ++g) {
-            const size_t x = ch[g];
-            auto slot = [&](int s, size_t y) {
-                valid |= 1u << s;
-                box[s] = y;
-                codes[s] = meta(y) > 0 ? leaf_code(y) : qcode(y);
-                if (slot_node) (*slot_node)[4 * qi + (size_t)s] = (int32_t)y;
-            };
-            if (meta(x) <= 0 && inside(x + 1, x) && inside((size_t)link(x), x)) {
-                slot(2 * g, x + 1);
-                slot(2 * g + 1, (size_t)link(x));
-                axes[g] = (uint32_t)(-meta(x) - 1);
-            } else {
-                slot(2 * g, x);
-            }
-        }
-        for (int s = 0; s < 4; ++s) {
-            const DNode& b = nodes[box[s]];
-            Q.lox[s] = b.lo[0]; Q.hix[s] = b.hi[0];
-            Q.loy[s] = b.lo[1]; Q.hiy[s] = b.hi[1];
-            Q.loz[s] = b.lo[2]; Q.hiz[s] = b.hi[2];
-            Q.code[s] = bits_to_float(codes[s]);
-        }
-        const uint32_t m = valid | ((uint32_t)(-meta(i) - 1) << 4) | (axes[0] << 6) | (axes[1] << 8);
-        Q.meta[0] = bits_to_float((int32_t)m);
-    }
-    // stack bound: children quads come later in DFS order, so a reverse sweep sees them first
-    root_occ = 0;
-    for (size_t qi = order.size(); qi-- > 0;) {
-        const DQuad& Q = quads[qi];
-        const uint32_t m = (uint32_t)__float_as_int_host(Q.meta[0]);
-        int32_t deepest = 0, nv = 0;
-        for (int s = 0; s < 4; ++s) {
-            if (!((m >> s) & 1u)) continue;
-            ++nv;
-            const int32_t cd = __float_as_int_host(Q.code[s]);
-            if (cd >= 0) deepest = std::max(deepest, occ[(size_t)(cd & kQuadIdxMask)]);
-        }
-        occ[qi] = nv - 1 + deepest;
-        root_occ = occ[qi];
-    }
-    if (order.empty()) root_occ = 0;
-    root_code = meta(0) > 0 ? leaf_code(0) : qcode(0);
-    return root_occ <= 64;   // HybStack holds rows + 64 >= 64 entries
-}
-
-// IEEE binary16 bits of x >= 0 rounded down (toward 0) or up (toward +inf; +inf past the range).
-uint16_t half_dir(double x, bool up) {
-    if (!(x >= 0.0)) return up ? (uint16_t)0x7c00 : (uint16_t)0;
-    auto val = [](uint16_t bits) {
-        _Float16 t;
-        std::memcpy(&t, &bits, 2);
-        return (double)t;
-    };
-    const _Float16 h = (_Float16)(float)x;
-    uint16_t b;
-    std::memcpy(&b, &h, 2);
-    if (up) {
-        while (b < 0x7c00 && val(b) < x) ++b;
-    } else {
-        while (b > 0 && val(b) > x) --b;
-    }
-    return b;
-}
-
-// Exact t-cull margins of the 4-wide walk (DESIGN.md §4.3 "exact t-cull").  For a triangle with
-// float edges e1, e2 that glm::intersectRayTriangle reports hit (gtx/intersect.inl:37-74: the
-// determinant a >= FLT_EPSILON, barycentrics in range), its computed t satisfies
-//     t >= (tau_min(B) - (g lambda + 4.8 u) diam / |d|) / (1 + g),   g = c (1 + u) / (1 - c),
-//     c = (1 + u)(9 |e1||e2| |d| + 1.74 u),  lambda = 1 + 3.01 u,  diam = max(|e1|, |e2|),
-// for every box B that holds the triangle, tau_min(B) = min over B of (X - o).d / |d|^2 (u = 2^-24).
-// Per quad slot (a node of the reference tree) with the maxima of |e1||e2| and diam over its
-// subtree: the slot's children are culled when A tau_lo > B + best (with relative slack), where
-// A = 1 / ((1 + g)(1 + 2^-18)) (|d|^2 in [1 - 2^-18, 1 + 2^-18], checked per ray) rounded down and
-// B = (g lambda + 4.8 u) diam / ((1 - 2^-19)(1 + g)) rounded up, both as binary16: one 32-bit word
-// per slot, A | B << 16.  c >= 1 (large triangles): A = 0, B = inf, never culled.
-// Returns the fraction of valid slots with A >= 1/2 (the share where the cull can pay).
-double build_qcull(const std::vector<DNode>& nodes, const std::vector<pt_triangle>& tris,
-                   const std::vector<int32_t>& slot_node, std::vector<uint32_t>& qcull) {
-    const size_t n = nodes.size();
-    std::vector<double> mmax(n, 0.0), dmax(n, 0.0);
-    for (size_t i = n; i-- > 0;) {
-        const int32_t meta = __float_as_int_host(nodes[i].lo[3]), link = __float_as_int_host(nodes[i].hi[3]);
-        if (meta > 0) {
-            for (int32_t k = link; k < link + meta && (size_t)k < tris.size(); ++k) {
-                const pt_triangle& t = tris[(size_t)k];
-                double l1 = 0.0, l2 = 0.0;
-                for (int a = 0; a < 3; ++a) {
-                    const float e1 = t.v[1][a] - t.v[0][a], e2 = t.v[2][a] - t.v[0][a];   // the device's e1, e2
-                    l1 += (double)e1 * e1;
-                    l2 += (double)e2 * e2;
-                }
-                l1 = std::sqrt(l1) * (1.0 + 1e-12);
-                l2 = std::sqrt(l2) * (1.0 + 1e-12);
-                mmax[i] = std::max(mmax[i], l1 * l2 * (1.0 + 1e-12));
-                dmax[i] = std::max(dmax[i], std::max(l1, l2));
-                if (!std::isfinite(l1 * l2)) mmax[i] = HUGE_VAL;
-            }
-        } else if ((size_t)link < n && i + 1 < n) {
-            mmax[i] = std::max(mmax[i + 1], mmax[(size_t)link]);
-            dmax[i] = std::max(dmax[i + 1], dmax[(size_t)link]);
-        }
-    }
-    const double u = std::ldexp(1.0, -24), lam = 1.0 + 3.01 * u;
-    const double dhi = 1.0 + std::ldexp(1.0, -19), dlo = 1.0 - std::ldexp(1.0, -19);
-    qcull.assign(slot_node.size(), 0x7c000000u);   // A = 0, B = inf
-    size_t valid = 0, good = 0;
-    for (size_t k = 0; k < slot_node.size(); ++k) {
-        const int32_t y = slot_node[k];
-        if (y < 0) continue;
-        ++valid;
-        const double c = (1.0 + u) * (9.0 * mmax[(size_t)y] * dhi + 1.74 * u);
-        if (!(c < 1.0)) continue;
-        const double g = c * (1.0 + u) / (1.0 - c);
-        const double A = 1.0 / ((1.0 + g) * (1.0 + std::ldexp(1.0, -18))) * (1.0 - 1e-12);
-        const double B = (g * lam + 4.8 * u) * dmax[(size_t)y] / (dlo * (1.0 + g)) * (1.0 + 1e-12);
-        qcull[k] = (uint32_t)half_dir(A, false) | ((uint32_t)half_dir(B, true) << 16);
-        if (A >= 0.5) ++good;
-    }
-    return valid ? (double)good / (double)valid : 0.0;
-}
-
 int build_quads(pt_ctx* c, const std::vector<DNode>& nodes, const std::vector<pt_triangle>& tris) {
     std::vector<DQuad> quads;
     std::vector<int32_t> slot_node;
     int32_t root_code = 0, occ = 0;
-    if (!make_quads(nodes, quads, root_code, occ, &slot_node)) return PT_OK;
+    if (!pt::make_quads(nodes, quads, root_code, occ, &slot_node)) return PT_OK;
     DQuad* d_quads;
     if (int rc = c->alloc(&d_quads, quads.size())) return rc;
     HIP_TRY(hipMemcpy(d_quads, quads.data(), quads.size() * sizeof(DQuad), hipMemcpyHostToDevice));
@@ -4401,7 +3716,7 @@ int build_quads(pt_ctx* c, const std::vector<DNode>& nodes, const std::vector<pt
     c->quad_occ = occ;
     // exact t-cull: on when at least a quarter of the slots can cull (A >= 1/2), PT_AMD_TCULL=0/1 forces
     std::vector<uint32_t> qcull;
-    c->tcull_frac = build_qcull(nodes, tris, slot_node, qcull);
+    c->tcull_frac = pt::build_qcull(nodes, tris, slot_node, qcull);
     bool on = c->tcull_frac >= 0.25;
     if (const char* e = std::getenv("PT_AMD_TCULL")) on = std::strcmp(e, "1") == 0;
     c->args.S.qcull = nullptr;
@@ -4418,33 +3733,12 @@ int build_quads(pt_ctx* c, const std::vector<DNode>& nodes, const std::vector<pt
     return PT_OK;
 }
 
-// SceneDev::bgeoms: the geom table stably ordered by bkind, each row keeping its index in `orig`;
-// among the world-box cubes the walls of the room come first (SceneDev::room_n of them).
+// SceneDev::bgeoms: the geom table in the order of the bounds pass (pt::bound_order).
 int upload_bound_order(pt_ctx* c) {
     std::vector<DGeom> b;
-    int32_t bk[6] = {0, 0, 0, 0, 0, 0};
-    const SceneDev& S = c->args.S;
-    auto wall = [&](size_t i) {   // a wall of the room (find_room)
-        for (int f = 0; f < 6; ++f)
-            if (S.room_n > 0 && S.room_tag[f] == (uint32_t)i) return true;
-        return false;
-    };
-    for (int k = 0; k < 5; ++k) {
-        bk[k] = (int32_t)b.size();
-        if (k == 3)   // the room's walls first among the world-box cubes
-            for (size_t i = 0; i < c->hgeoms.size(); ++i)
-                if (wall(i)) {
-                    b.push_back(c->hgeoms[i]);
-                    b.back().orig = (int32_t)i;
-                }
-        for (size_t i = 0; i < c->hgeoms.size(); ++i)
-            if (c->hgeoms[i].bkind == k && !(k == 3 && wall(i))) {
-                b.push_back(c->hgeoms[i]);
-                b.back().orig = (int32_t)i;
-            }
-    }
-    bk[5] = (int32_t)b.size();
-    if (b.size() != c->hgeoms.size()) return pt::fail(PT_ERR_ARG, "geom with an unknown bound kind");
+    int32_t bk[6];
+    pt::bound_order(c->bounds, b, bk);
+    if (b.size() != c->bounds.geoms.size()) return pt::fail(PT_ERR_ARG, "geom with an unknown bound kind");
     HIP_TRY(io_copy(c, c->d_bgeoms, b.data(), b.size() * sizeof(DGeom), hipMemcpyHostToDevice));
     c->args.S.bgeoms = c->d_bgeoms;
     for (int k = 0; k < 6; ++k) c->args.S.bk[k] = bk[k];
@@ -4484,73 +3778,10 @@ int pt_create(const pt_scene* scene, const pt_flags* flags, const pt_shard* shar
     set_flags_dev(c, flags ? *flags : [] { pt_flags f; pt_flags_default(&f); return f; }());
 
     // ---- scene upload ----
-    std::vector<DGeom> dg(S.geoms.size());
-    for (size_t i = 0; i < S.geoms.size(); ++i) {
-        const pt_geom& g = S.geoms[i];
-        DGeom& d = dg[i];
-        std::memset(&d, 0, sizeof d);
-        d.type = g.type;
-        d.material = g.material_id;
-        d.tri_start = g.tri_start;
-        d.tri_end = g.tri_end;
-        d.inv = to_affine(g.inverse_transform);
-        d.xf = to_affine(g.transform);
-        d.itr = to_affine(g.inv_transpose);
-        if (d.type == PT_GEOM_CUBE)   // DGeom::nrm: glm's multiplyMV + normalize of each unit axis, in float32
-            for (int code = 0; code < 6; ++code) {
-                const float sg = (code & 1) ? -1.0f : 1.0f;
-                const int a = code >> 1;
-                const float n[3] = {a == 0 ? sg : 0.0f, a == 1 ? sg : 0.0f, a == 2 ? sg : 0.0f};
-                float v[3];
-                for (int r = 0; r < 3; ++r)
-                    v[r] = (d.itr.c[0][r] * n[0] + d.itr.c[1][r] * n[1]) + (d.itr.c[2][r] * n[2] + d.itr.z3[r]);
-                const float inv = 1.0f / std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-                for (int r = 0; r < 3; ++r) d.nrm[code][r] = v[r] * inv;
-                // DGeom::frm: the hemisphere frame of that normal (float32, the device's cross/normalize)
-                const float* nn = d.nrm[code];
-                float dnn[3] = {0.0f, 0.0f, 1.0f};
-                if (std::fabs(nn[0]) < ptd::kSQRT_1_3) { dnn[0] = 1.0f; dnn[2] = 0.0f; }
-                else if (std::fabs(nn[1]) < ptd::kSQRT_1_3) { dnn[1] = 1.0f; dnn[2] = 0.0f; }
-                auto crs = [](const float* a, const float* b, float* o) {
-                    o[0] = a[1] * b[2] - b[1] * a[2];
-                    o[1] = a[2] * b[0] - b[2] * a[0];
-                    o[2] = a[0] * b[1] - b[0] * a[1];
-                };
-                auto nrmz = [](float* x) {
-                    const float iv = 1.0f / std::sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
-                    for (int r = 0; r < 3; ++r) x[r] = x[r] * iv;
-                };
-                float p1[3], p2[3];
-                crs(nn, dnn, p1);
-                nrmz(p1);
-                crs(nn, p1, p2);
-                nrmz(p2);
-                for (int r = 0; r < 3; ++r) { d.frm[code][r] = p1[r]; d.frm[code][3 + r] = p2[r]; }
-            }
-        for (int k = 0; k < 3; ++k) { d.bmin[k] = g.min_bound[k]; d.bmax[k] = g.max_bound[k]; }
-    }
-    {   // scene extent: every surface point (cube/sphere corners, mesh vertices) and the camera
-        double ext = 0.0;
-        for (int k = 0; k < 3; ++k) ext = std::max(ext, std::fabs((double)S.camera.position[k]));
-        for (const pt_geom& g : S.geoms) {
-            if (g.type != PT_GEOM_CUBE && g.type != PT_GEOM_SPHERE) continue;
-            for (int corner = 0; corner < 8; ++corner) {
-                const double p[3] = {corner & 1 ? 0.5 : -0.5, corner & 2 ? 0.5 : -0.5, corner & 4 ? 0.5 : -0.5};
-                for (int r = 0; r < 3; ++r) {
-                    double v = g.transform[12 + r];
-                    for (int k = 0; k < 3; ++k) v += (double)g.transform[4 * k + r] * p[k];
-                    ext = std::max(ext, std::fabs(v));
-                }
-            }
-        }
-        for (const pt_triangle& t : S.triangles)
-            for (int v = 0; v < 3; ++v)
-                for (int k = 0; k < 3; ++k) ext = std::max(ext, std::fabs((double)t.v[v][k]));
-        c->scene_ext = ext;
-    }
-    c->hgeoms = dg;
-    update_bounds(c, c->flags.aperture);
-    dg = c->hgeoms;
+    c->bounds = pt::make_dgeoms(S);
+    pt::update_bounds(c->bounds, c->flags.aperture);
+    sync_bounds(c);
+    const std::vector<DGeom>& dg = c->bounds.geoms;
     DGeom* d_geoms;
     DMaterial* d_mats;
     if (int rc = c->alloc(&d_geoms, dg.size())) return bail(rc);
@@ -4607,7 +3838,7 @@ int pt_create(const pt_scene* scene, const pt_flags* flags, const pt_shard* shar
         A.S.ntris = (int)tr.size();
     }
     if (!S.bvh.empty()) {
-        const std::vector<DNode> nodes = to_dnodes(S.bvh);
+        const std::vector<DNode> nodes = pt::to_dnodes(S.bvh);
         DNode* d_nodes;
         if (int rc = c->alloc(&d_nodes, nodes.size())) return bail(rc);
         if ((e = hipMemcpy(d_nodes, nodes.data(), nodes.size() * sizeof(DNode), hipMemcpyHostToDevice)) != hipSuccess)
@@ -4914,8 +4145,9 @@ int pt_set_flags(pt_ctx* c, const pt_flags* f) {
     if (int rc = wait_ctx(c)) return rc;
     if (c->ahead_recorded) HIP_TRY(hipEventSynchronize(c->ev_ahead));   // (and is dropped: flags differ)
     if (lens) {   // the camera lens bounds the ray origins: re-derive the widened bounds
-        update_bounds(c, f->aperture);
-        HIP_TRY(io_copy(c, c->d_geoms, c->hgeoms.data(), c->hgeoms.size() * sizeof(DGeom), hipMemcpyHostToDevice));
+        pt::update_bounds(c->bounds, f->aperture);
+        sync_bounds(c);
+        HIP_TRY(io_copy(c, c->d_geoms, c->bounds.geoms.data(), c->bounds.geoms.size() * sizeof(DGeom), hipMemcpyHostToDevice));
         if (int rc = upload_bound_order(c)) return rc;
     }
     return build_cmask(c);   // SSAA / DoF / aperture / focal distance bound the camera rays
@@ -4939,13 +4171,7 @@ int pt_ctx_cmask_info(const pt_ctx* c, int32_t* on, double* empty_frac, int32_t*
 
 int pt_ctx_room_info(const pt_ctx* c, int32_t* walls, int32_t* faces, float* lo, float* hi) {
     if (!c) return pt::fail(PT_ERR_ARG, "null context");
-    const SceneDev& S = c->args.S;
-    if (walls) *walls = S.room_n;
-    for (int f = 0; f < 6 && faces; ++f) faces[f] = S.room_n > 0 && S.room_tag[f] < 32u ? (int32_t)S.room_tag[f] : -1;
-    for (int a = 0; a < 3; ++a) {
-        if (lo) lo[a] = S.room_pl[2 * a];
-        if (hi) hi[a] = S.room_pl[2 * a + 1];
-    }
+    pt::room_info(c->args.S.room, walls, faces, lo, hi);
     return PT_OK;
 }
 
@@ -5621,33 +4847,6 @@ int pt_debug_trav(unsigned long long* out8, int32_t reset) {
     return PT_OK;
 }
 #endif
-
-int pt_scene_bvh_quads(const pt_scene* scene, void* out, int32_t cap, int32_t* root_code, int32_t* stack_bound) {
-    if (!scene) return -PT_ERR_ARG;
-    const auto& S = *reinterpret_cast<const pt::Scene*>(scene);
-    std::vector<DQuad> quads;
-    int32_t rc = 0, occ = 0;
-    if (!make_quads(to_dnodes(S.bvh), quads, rc, occ)) return 0;
-    if (root_code) *root_code = rc;
-    if (stack_bound) *stack_bound = occ;
-    if (out && cap > 0) std::memcpy(out, quads.data(), std::min<size_t>((size_t)cap, quads.size()) * sizeof(DQuad));
-    return (int)quads.size();
-}
-
-int pt_scene_bvh_tcull(const pt_scene* scene, uint32_t* words, int32_t cap, double* cullable_frac) {
-    if (!scene) return -PT_ERR_ARG;
-    const auto& S = *reinterpret_cast<const pt::Scene*>(scene);
-    std::vector<DQuad> quads;
-    std::vector<int32_t> slot_node;
-    int32_t rc = 0, occ = 0;
-    const std::vector<DNode> nodes = to_dnodes(S.bvh);
-    if (!make_quads(nodes, quads, rc, occ, &slot_node)) return 0;
-    std::vector<uint32_t> q;
-    const double frac = build_qcull(nodes, S.triangles, slot_node, q);
-    if (cullable_frac) *cullable_frac = frac;
-    if (words && cap > 0) std::memcpy(words, q.data(), std::min<size_t>((size_t)cap, q.size()) * sizeof(uint32_t));
-    return (int)q.size();
-}
 
 int pt_selftest_math(uint64_t n, uint32_t seed, uint64_t* mismatches) {
     if (!mismatches) return pt::fail(PT_ERR_ARG, "null argument");

@@ -6,8 +6,8 @@ the light and the open front make per-row cost uneven), scene data is replicated
 collective is ONE gather of the float accumulators to rank 0 when the image is saved.  Message
 per rank: ceil(H / world) * W * 12 bytes.
 
-The device side of the partition lives in pt_kernels.hip (TileDev: global pixel index of a tile
-row); this module is the host side: row bookkeeping, padding and the gather.  It is backend
+The device side of the partition lives in the kernels (pt_layout.h TileDev: global pixel index of a
+tile row); this module is the host side: row bookkeeping, padding and the gather.  It is backend
 agnostic — RCCL ("nccl") on the GPU box, gloo in the CPU tests.
 """
 from __future__ import annotations

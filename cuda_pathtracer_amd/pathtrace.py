@@ -223,6 +223,18 @@ class Scene:
         lib().pt_scene_get_geoms(self._h, arr, ng)
         return list(arr)[:ng]
 
+    def room_info(self, gui: GuiDataContainer | None = None) -> dict:
+        """The room a PathTracer of this scene with these flags would bound as one group
+        (pt_scene_room_info: the host's scene preparation alone, no device), as PathTracer.room_info."""
+        if not hasattr(lib(), "pt_scene_room_info"):
+            raise N.NativeLibraryError("the loaded library (PT_AMD_LIB) predates pt_scene_room_info")
+        flags = (gui or GuiDataContainer()).to_c()
+        n, faces = C.c_int32(), (C.c_int32 * 6)()
+        lo, hi = (C.c_float * 3)(), (C.c_float * 3)()
+        check_pt(lib().pt_scene_room_info(self._h, C.byref(flags), C.byref(n), faces, lo, hi))
+        return {"walls": int(n.value), "faces": [int(v) for v in faces], "lo": [float(v) for v in lo],
+                "hi": [float(v) for v in hi]}
+
     def materials(self):
         nm = self.counts()[1]
         arr = (N.Material * max(nm, 1))()

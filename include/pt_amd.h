@@ -221,7 +221,7 @@ int pt_scene_get_triangles(const pt_scene* s, pt_triangle* out, int32_t cap);
 int pt_scene_get_bvh(const pt_scene* s, pt_bvh_node* out, int32_t cap);
 /* Inspection (host only, used by the tests): the 4-wide layout the BVH walk of mesh scenes runs on
  * (128-byte entries: lo.x, hi.x, lo.y, hi.y, lo.z, hi.z, codes, meta — each 4 slots; layout and
- * codes in pt_kernels.hip DQuad).  Returns the entry count (0: no 4-wide layout for this tree; the
+ * codes in pt_layout.h DQuad).  Returns the entry count (0: no 4-wide layout for this tree; the
  * pair walk runs) and copies min(count, cap) entries; *root_code / *stack_bound as pt_create uses. */
 int pt_scene_bvh_quads(const pt_scene* s, void* out, int32_t cap, int32_t* root_code, int32_t* stack_bound);
 /* Inspection (host only): the 4-wide walk's exact t-cull words, 4 per quad in pt_scene_bvh_quads's
@@ -229,6 +229,10 @@ int pt_scene_bvh_quads(const pt_scene* s, void* out, int32_t cap, int32_t* root_
  * when A * tau_lo > B + best), and the share of slots with A >= 1/2.  Returns the word
  * count (0: no 4-wide layout) and copies min(count, cap) words. */
 int pt_scene_bvh_tcull(const pt_scene* s, uint32_t* words, int32_t cap, double* cullable_frac);
+/* Inspection (host only): the room a context created from this scene with these flags (NULL: the
+ * defaults) would bound as one group, derived without a device; outputs as pt_ctx_room_info's. */
+int pt_scene_room_info(const pt_scene* s, const pt_flags* flags, int32_t* walls, int32_t* faces, float* lo,
+                       float* hi);
 
 /* ---- render context -------------------------------------------------------------------- */
 /* pathtraceInit: uploads the scene to the current HIP device, allocates SoA path buffers for

@@ -5,6 +5,8 @@ set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 B=$R/cuda_pathtracer_amd/build
 python -c "import sys; sys.path.insert(0, '$R'); from cuda_pathtracer_amd import build; build.build_native()"
+# the library's other objects, as build.py lists them
+others=$(python -c "import sys; sys.path.insert(0, '$R'); from cuda_pathtracer_amd import build; print(*build.other_objs('pt_kernels.hip'))")
 for v in $VARIANTS; do
   name=${v%%:*}; flags=$(echo ${v#*:} | tr ',' ' ')
   /opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize $flags -I $R/include \
@@ -14,7 +16,6 @@ done
 for p in $pids; do wait $p || { echo "variant compile failed" >&2; exit 1; }; done
 for v in $VARIANTS; do
   name=${v%%:*}
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $B/libpt_amd_$name.so $B/pt_kernels_$name.o \
-      $B/sc_kernels.hip.o $B/sc_variants.hip.o $B/bvh_build.hip.o $B/pt_denoise.hip.o $B/pt_scene.cpp.o $B/pt_mesh.cpp.o $B/pt_image.cpp.o $B/pt_jpeg.cpp.o -lz
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $B/libpt_amd_$name.so $B/pt_kernels_$name.o $others -lz
   echo $B/libpt_amd_$name.so
 done

@@ -1,4 +1,4 @@
-"""The 4-wide BVH layout k_traverse4 walks (pt_kernels.hip DQuad, built by the product's host code
+"""The 4-wide BVH layout k_traverse4 walks (pt_layout.h DQuad, built by pt_bvh_layout.cpp
 and read back through pt_scene_bvh_quads) against the reference's binary walk, on the CPU.
 
 BVHIntersectionTest (intersections.cu:170-224; BoundingBox::intersect boundingbox.h:73-92) visits

@@ -861,7 +861,7 @@ def test_two_lanes_equal_one_lane(cornell_path, monkeypatch, spp, lanes, sort):
     (((192, 64), 45.0, (0, 5, 10.5), (14, 5, 0)), dict(sortbyMaterial=True), (0, 1)),
 ])
 def test_first_bounce_camera_masks(cornell_path, monkeypatch, cam, kw, shard):
-    """First-bounce geom masks (pt_kernels.hip build_cmask): each wave of camera rays bounds only
+    """First-bounce geom masks (pt_bounds.cpp camera_masks): each wave of camera rays bounds only
     the geoms its 64 pixels' rays can reach.  Odd widths, shards, wide apertures, cameras inside the
     scene and grazing views: GPU == oracle bit for bit, and == the same context without masks
     (PT_AMD_NO_CMASK=1).  Then flags changed through pt_set_flags (masks rebuilt) still match."""

@@ -1,5 +1,5 @@
-"""The departure claim of the room's grouped bound (pt_kernels.hip bound_room_tagged, find_room's
-room_in).
+"""The departure claim of the room's grouped bound (pt_kernels.hip bound_room_tagged, pt_bounds.cpp
+find_room's room.in).
 
 A ray that has just left a wall starts inside that wall's padded world slab, so the grouped bound
 used to keep the wall as a candidate with bound 0 and the whole wave ran an exact test that always

@@ -114,8 +114,8 @@ import pytest   # noqa: E402
 
 @pytest.mark.parametrize("scene", ["tessellated", "config5"])
 def test_tcull_margins_only_skip_worse_hits(tmp_path, scene):
-    """The walk's exact t-cull (pt_kernels.hip k_traverse4; margins from build_qcull, DESIGN.md
-    §4.3) enters no slot whose margin says A * tau_lo > B + best.  For leaf slots of the tessellated
+    """The walk's exact t-cull (pt_kernels.hip k_traverse4; margins from pt_bvh_layout.cpp build_qcull,
+    DESIGN.md §4.3) enters no slot whose margin says A * tau_lo > B + best.  For leaf slots of the tessellated
     scene (the cull's case) and of config 5 (whose large triangles mostly get no margin), rays aimed
     at the leaf's triangles — a third of them grazing the triangle's plane at the FLT_EPSILON
     threshold — must give every computed glm t at or above the largest `best` the slot would be
