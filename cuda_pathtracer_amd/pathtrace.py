@@ -223,6 +223,15 @@ class Scene:
         lib().pt_scene_get_geoms(self._h, arr, ng)
         return list(arr)[:ng]
 
+    def triangles(self):
+        """The world-space mesh triangles in BVH leaf order, each with its load-order id
+        (pt_scene_get_triangles)."""
+        nt = self.counts()[2]
+        arr = (N.Triangle * max(nt, 1))()
+        if lib().pt_scene_get_triangles(self._h, arr, nt) != nt:
+            raise RuntimeError("pt_scene_get_triangles: triangle count changed")
+        return list(arr)[:nt]
+
     def room_info(self, gui: GuiDataContainer | None = None) -> dict:
         """The room a PathTracer of this scene with these flags would bound as one group
         (pt_scene_room_info: the host's scene preparation alone, no device), as PathTracer.room_info."""

@@ -96,6 +96,59 @@ def camera_rays(cam, dt):
     return _normalize(d.astype(dt), dt)
 
 
+def geom_hit(g, ob, d, dt, edge_eps):
+    """One sphere (type 0) or cube (type 1) against the rays (ob, d), every step in dtype dt:
+    (world distance, inf on a miss; normal; risky whether hit or not; risky if this is the closest hit)."""
+    shape = d.shape[:-1]
+    always = np.zeros(shape, bool)
+    qo = _mv(g.inverse_transform, ob, 1, dt)
+    qd = _normalize(_mv(g.inverse_transform, d, 0, dt), dt)
+    if g.type == 1:
+        tmin = np.full(shape, -1e38, dt)
+        tmax = np.full(shape, 1e38, dt)
+        nmin = np.zeros(shape + (3,), dt)
+        nmax = np.zeros(shape + (3,), dt)
+        for a in range(3):
+            t1 = (dt(-0.5) - qo[..., a]) / qd[..., a]
+            t2 = (dt(0.5) - qo[..., a]) / qd[..., a]
+            ta, tb = np.minimum(t1, t2), np.maximum(t1, t2)
+            n = np.zeros(shape + (3,), dt)
+            n[..., a] = np.where(t2 < t1, dt(1), dt(-1))
+            up_ = (ta > 0) & (ta > tmin)
+            tmin = np.where(up_, ta, tmin)
+            nmin = np.where(up_[..., None], n, nmin)
+            lo = tb < tmax
+            tmax = np.where(lo, tb, tmax)
+            nmax = np.where(lo[..., None], n, nmax)
+        always |= np.abs(tmax - tmin) < 4 * edge_eps     # grazes an edge or corner, hit or miss
+        hit = (tmax >= tmin) & (tmax > 0)
+        inside = tmin <= 0
+        tmin = np.where(inside, tmax, tmin)
+        nmin = np.where(inside[..., None], nmax, nmin)
+        obj = qo + (tmin - dt(0.0001))[..., None] * _normalize(qd, dt)
+        near = (np.abs(np.abs(qo + tmin[..., None] * qd) - 0.5) < edge_eps).sum(axis=-1)
+        edge = hit & (near >= 2)
+        nrm = _normalize(_mv(g.inv_transpose, nmin, 0, dt), dt)
+    else:
+        vdd = _dot(qo, qd)
+        rad = vdd * vdd - (_dot(qo, qo) - dt(0.25))
+        always |= np.abs(rad) < edge_eps
+        sq = np.sqrt(np.where(rad < 0, dt(0), rad))
+        t1, t2 = -vdd + sq, -vdd - sq
+        hit = (rad >= 0) & ~((t1 < 0) & (t2 < 0))
+        outside = (t1 > 0) & (t2 > 0)
+        t = np.where(outside, np.minimum(t1, t2), np.maximum(t1, t2))
+        obj = qo + (t - dt(0.0001))[..., None] * _normalize(qd, dt)
+        nrm = _normalize(_mv(g.inv_transpose, obj, 0, dt), dt)
+        nrm = np.where(outside[..., None], nrm, -nrm)
+        edge = np.zeros(shape, bool)
+    ip = _mv(g.transform, obj, 1, dt)
+    diff = ob - ip
+    tw = np.sqrt(_dot(diff, diff))
+    hit &= tw > 0
+    return np.where(hit, tw, np.inf), nrm, always, edge
+
+
 def first_hit_ref(geoms, cam, dt=np.float64, edge_eps=1e-3):
     """Closest hit over the scene's spheres (type 0) and cubes (type 1), every step in dtype dt.
     Returns dict(mat (-1 miss), n, t, P, keep): keep is False where the ray passes within edge_eps
@@ -113,52 +166,8 @@ def first_hit_ref(geoms, cam, dt=np.float64, edge_eps=1e-3):
         risky = np.zeros(shape, bool)
         ob = np.broadcast_to(o, d.shape)
         for g in geoms:
-            qo = _mv(g.inverse_transform, ob, 1, dt)
-            qd = _normalize(_mv(g.inverse_transform, d, 0, dt), dt)
-            if g.type == 1:
-                tmin = np.full(shape, -1e38, dt)
-                tmax = np.full(shape, 1e38, dt)
-                nmin = np.zeros(shape + (3,), dt)
-                nmax = np.zeros(shape + (3,), dt)
-                for a in range(3):
-                    t1 = (dt(-0.5) - qo[..., a]) / qd[..., a]
-                    t2 = (dt(0.5) - qo[..., a]) / qd[..., a]
-                    ta, tb = np.minimum(t1, t2), np.maximum(t1, t2)
-                    n = np.zeros(shape + (3,), dt)
-                    n[..., a] = np.where(t2 < t1, dt(1), dt(-1))
-                    up_ = (ta > 0) & (ta > tmin)
-                    tmin = np.where(up_, ta, tmin)
-                    nmin = np.where(up_[..., None], n, nmin)
-                    lo = tb < tmax
-                    tmax = np.where(lo, tb, tmax)
-                    nmax = np.where(lo[..., None], n, nmax)
-                risky |= np.abs(tmax - tmin) < 4 * edge_eps     # grazes an edge or corner, hit or miss
-                hit = (tmax >= tmin) & (tmax > 0)
-                inside = tmin <= 0
-                tmin = np.where(inside, tmax, tmin)
-                nmin = np.where(inside[..., None], nmax, nmin)
-                obj = qo + (tmin - dt(0.0001))[..., None] * _normalize(qd, dt)
-                near = (np.abs(np.abs(qo + tmin[..., None] * qd) - 0.5) < edge_eps).sum(axis=-1)
-                edge = hit & (near >= 2)
-                nrm = _normalize(_mv(g.inv_transpose, nmin, 0, dt), dt)
-            else:
-                vdd = _dot(qo, qd)
-                rad = vdd * vdd - (_dot(qo, qo) - dt(0.25))
-                risky |= np.abs(rad) < edge_eps
-                sq = np.sqrt(np.where(rad < 0, dt(0), rad))
-                t1, t2 = -vdd + sq, -vdd - sq
-                hit = (rad >= 0) & ~((t1 < 0) & (t2 < 0))
-                outside = (t1 > 0) & (t2 > 0)
-                t = np.where(outside, np.minimum(t1, t2), np.maximum(t1, t2))
-                obj = qo + (t - dt(0.0001))[..., None] * _normalize(qd, dt)
-                nrm = _normalize(_mv(g.inv_transpose, obj, 0, dt), dt)
-                nrm = np.where(outside[..., None], nrm, -nrm)
-                edge = np.zeros(shape, bool)
-            ip = _mv(g.transform, obj, 1, dt)
-            diff = ob - ip
-            tw = np.sqrt(_dot(diff, diff))
-            hit &= tw > 0
-            tw = np.where(hit, tw, np.inf)
+            tw, nrm, always, edge = geom_hit(g, ob, d, dt, edge_eps)
+            risky |= always
             closer = tw < best_t
             second_t = np.where(closer, best_t, np.minimum(second_t, tw))
             best_t = np.where(closer, tw, best_t)
@@ -184,6 +193,25 @@ def three_body_scene(P, res=(40, 30)):
     s.add_geom(P.SPHERE, m[2], (0.2, 5.3, 1.5), (0.0, 30.0, 40.0), (2.2, 1.4, 1.8))
     s.set_camera(res, 20.0, (0.0, 5.0, 10.5), (0.2, 5.0, 0.0), (0.0, 1.0, 0.0))
     s.set_render(1, 4, "three_body")
+    s.finalize()
+    return s
+
+
+def inside_scene(P, shell, res=(40, 30)):
+    """The camera inside a stretched, rotated sphere (shell = P.SPHERE) or a rotated cube (P.CUBE), with
+    a cube and a sphere in front of it: every ray that passes them meets the shell from within
+    (intersections.cu:46-51 and 99-112, outside = false).  Materials 1..3; there are no misses."""
+    s = P.Scene()
+    s.add_material(rgb=(0.1, 0.1, 0.1))
+    m = [s.add_material(rgb=c) for c in ((0.8, 0.3, 0.2), (0.2, 0.7, 0.3), (0.3, 0.4, 0.9))]
+    if shell == P.SPHERE:
+        s.add_geom(P.SPHERE, m[0], (0.0, 5.0, 0.0), (0.0, 30.0, 40.0), (24.0, 14.0, 20.0))
+    else:
+        s.add_geom(P.CUBE, m[0], (0.0, 5.0, 0.0), (10.0, 25.0, 5.0), (20.0, 12.0, 24.0))
+    s.add_geom(P.CUBE, m[1], (-1.6, 4.4, 0.5), (20.0, 35.0, 10.0), (1.5, 1.2, 1.8))
+    s.add_geom(P.SPHERE, m[2], (1.5, 5.6, 1.0), (0.0, 30.0, 40.0), (1.6, 1.0, 1.3))
+    s.set_camera(res, 20.0, (0.0, 5.0, 6.0), (0.2, 5.0, 0.0), (0.0, 1.0, 0.0))
+    s.set_render(1, 4, "inside")
     s.finalize()
     return s
 

@@ -8,6 +8,8 @@ sphere and cube tests, within 8x the error the same restatement shows when evalu
 Measured on the CPU (float32 restatement against float64, kept pixels; tests/denoise_ref.py deviations):
     sphere.json, 40x30, camera moved in:   D_n = 2.76e-5   D_t = 4.40e-6   D_p = 3.98e-6
     three_body_scene, 40x30:               D_n = 3.99e-5   D_t = 4.45e-6   D_p = 4.40e-6
+    inside_scene (sphere shell), 40x30:    D_n = 3.53e-5   D_t = 4.93e-6   D_p = 4.59e-6
+    inside_scene (cube shell), 40x30:      D_n = 3.53e-5   D_t = 4.93e-6   D_p = 4.59e-6
 (the 1e-4 back-off of getPointOnRay is subtracted from an object-space parameter of order 10, and the
 normal of a stretched sphere comes from that point: a few ulp of 10 through the inverse-transpose.)
 The constants below are those, rounded up; the GPU may deviate by 8x them.
@@ -34,9 +36,9 @@ SCENES = ROOT / "tests" / "scenes"
 F = np.float32
 PT_ERR_ARG = 1
 
-D_N = {"sphere": 2.8e-5, "three": 4.0e-5}
-D_T = {"sphere": 4.5e-6, "three": 4.5e-6}
-D_P = {"sphere": 4.0e-6, "three": 4.5e-6}
+D_N = {"sphere": 2.8e-5, "three": 4.0e-5, "inside_sphere": 3.6e-5, "inside_cube": 3.6e-5}
+D_T = {"sphere": 4.5e-6, "three": 4.5e-6, "inside_sphere": 5.0e-6, "inside_cube": 5.0e-6}
+D_P = {"sphere": 4.0e-6, "three": 4.5e-6, "inside_sphere": 4.6e-6, "inside_cube": 4.6e-6}
 
 
 # ---- the filter, bit for bit ------------------------------------------------------------------------
@@ -246,17 +248,22 @@ def _geometry_scene(tmp_path, which):
     if which == "sphere":   # the bundled scene, its camera moved in so that the sphere fills a fifth of the frame
         return P.Scene(_scene_file(tmp_path, "sphere", RES=[40, 30], FOVY=14.0, EYE=[1.0, 4.0, 10.5],
                                    LOOKAT=[0.3, 0.4, 0.0]))
+    if which.startswith("inside"):   # the camera within the shell: the outside = false branches of both tests
+        return R.inside_scene(P, P.SPHERE if which == "inside_sphere" else P.CUBE)
     return R.three_body_scene(P)
 
 
-@pytest.mark.parametrize("which", ["sphere", "three"])
+@pytest.mark.parametrize("which", ["sphere", "three", "inside_sphere", "inside_cube"])
 def test_gbuffer_geometry_within_8x_of_float32s_own_error(tmp_path, gpu_device, which):
     scene = _geometry_scene(tmp_path, which)
     ref = R.first_hit_ref(scene.geoms(), scene.camera(), np.float64)
     ref32 = R.first_hit_ref(scene.geoms(), scene.camera(), np.float32)
     keep = ref["keep"]
     assert 1.0 - keep.mean() <= 0.05                      # (float64 side alone)
-    assert (ref["mat"] >= 0).mean() > 0.1 and (ref["mat"] < 0).any()
+    if which.startswith("inside"):                        # closed: the shell (material 1) behind everything
+        assert (ref["mat"] >= 0).all() and (ref["mat"] == 1).mean() > 0.5 and len(np.unique(ref["mat"])) == 3
+    else:
+        assert (ref["mat"] >= 0).mean() > 0.1 and (ref["mat"] < 0).any()
     d_n, d_t, d_p = R.deviations(ref, ref32)
     print(f"{which}: D_n={d_n:.3e} D_t={d_t:.3e} D_p={d_p:.3e} excluded={1 - keep.mean():.4f}")
     assert d_n <= D_N[which] and d_t <= D_T[which] and d_p <= D_P[which]
