@@ -109,7 +109,20 @@ class TemporalParams(C.Structure):
         return p
 
 
+class AdaptiveParams(C.Structure):
+    """pt_adaptive_params; AdaptiveParams.default() = pt_adaptive_params_default."""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("min_batches", C.c_int32), ("dilate", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+    @classmethod
+    def default(cls) -> "AdaptiveParams":
+        p = cls()
+        lib().pt_adaptive_params_default(C.byref(p))
+        return p
+
+
 assert C.sizeof(DenoiseParams) == 32 and C.sizeof(DenoiseVarParams) == 32 and C.sizeof(TemporalParams) == 32
+assert C.sizeof(AdaptiveParams) == 32
 assert C.sizeof(Geom) == 272 and C.sizeof(Material) == 48 and C.sizeof(Triangle) == 124
 assert C.sizeof(BvhNode) == 40
 
@@ -239,6 +252,24 @@ SIGNATURES = {
     "pt_temporal_get": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "pt_temporal_frame_ctx": (_I, [_P, _P, _F, _P]),
     "pt_temporal_image": (_I, [_P, C.POINTER(DenoiseVarParams), _P, _P, _P]),
+    "pt_adaptive_params_default": (None, [C.POINTER(AdaptiveParams)]),
+    "pt_adaptive_obj_create": (_I, [_I, _I, C.POINTER(_P)]),
+    "pt_adaptive_obj_destroy": (_I, [_P]),
+    "pt_adaptive_obj_info": (_I, [_P, _IP, _IP, _FP]),
+    "pt_adaptive_obj_reset": (_I, [_P, _P, _P]),
+    "pt_adaptive_obj_update": (_I, [_P, _P, _F, _P, _P]),
+    "pt_adaptive_obj_select": (_I, [_P, C.POINTER(AdaptiveParams), _P, _IP, _IP]),
+    "pt_adaptive_obj_set_mask": (_I, [_P, _P, _I, _P]),
+    "pt_adaptive_obj_apply": (_I, [_P, _P, _P, _P]),
+    "pt_adaptive_obj_resolve": (_I, [_P, _P, _P, _P, _P]),
+    "pt_adaptive_obj_get": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "pt_adaptive_enable": (_I, [_P, _I]),
+    "pt_adaptive_update": (_I, [_P, _I, _P]),
+    "pt_adaptive_select": (_I, [_P, C.POINTER(AdaptiveParams), _IP, _IP]),
+    "pt_adaptive_set_mask": (_I, [_P, _P, _I]),
+    "pt_adaptive_info": (_I, [_P, _IP, _IP, _IP, _IP, _FP]),
+    "pt_adaptive_get": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "pt_adaptive_image": (_I, [_P, C.POINTER(DenoiseVarParams), _P, _P]),
 }
 
 _lib = None
@@ -257,7 +288,7 @@ def _preload_torch() -> None:
 # Entry points an older library may lack when PT_AMD_LIB times it beside this tree (the shipped
 # library has them all; pt_ctx_room_info: the A/B against the build before the room bound;
 # pt_scene_room_info: the A/B against the build before the host-only bounds unit; the
-# variance entry points and pt_temporal_*: the A/B against the builds before them;
+# variance entry points, pt_temporal_* and pt_adaptive_*: the A/B against the builds before them;
 # pt_ctx_depart_counts: the A/B against the build before the room's departure claim).
 _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
              "pt_moments_create",
@@ -266,7 +297,12 @@ _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "p
              "pt_track_variance", "pt_variance_update", "pt_variance_info", "pt_get_variance", "pt_denoise_image_var",
              "pt_temporal_params_default", "pt_temporal_create", "pt_temporal_destroy", "pt_temporal_reset",
              "pt_temporal_info", "pt_temporal_frame", "pt_temporal_resolve", "pt_temporal_frame_host", "pt_temporal_get",
-             "pt_temporal_frame_ctx", "pt_temporal_image"}
+             "pt_temporal_frame_ctx", "pt_temporal_image",
+             "pt_adaptive_params_default", "pt_adaptive_obj_create", "pt_adaptive_obj_destroy", "pt_adaptive_obj_info",
+             "pt_adaptive_obj_reset", "pt_adaptive_obj_update", "pt_adaptive_obj_select", "pt_adaptive_obj_set_mask",
+             "pt_adaptive_obj_apply", "pt_adaptive_obj_resolve", "pt_adaptive_obj_get", "pt_adaptive_enable",
+             "pt_adaptive_update", "pt_adaptive_select", "pt_adaptive_set_mask", "pt_adaptive_info", "pt_adaptive_get",
+             "pt_adaptive_image"}
 
 
 def lib() -> C.CDLL:

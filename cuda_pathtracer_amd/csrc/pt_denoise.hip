@@ -25,6 +25,7 @@
 
 #include "pt_device.h"
 #include "pt_internal.h"
+#include "pt_moments_dev.h"
 
 using namespace ptd;
 
@@ -33,7 +34,6 @@ namespace {
 constexpr int kTX = 32, kTY = 8, kThreads = kTX * kTY;
 constexpr int kLdsStep = 2;                       // largest step staged in LDS
 constexpr int kHX = kTX + 4 * kLdsStep, kHY = kTY + 4 * kLdsStep;
-constexpr float kAlbMin = 0x1p-10f;               // albedo components below are not (de)modulated
 constexpr int kMaxLevels = 8;
 constexpr int64_t kMaxPixels = (int64_t)1 << 30;
 
@@ -61,13 +61,6 @@ __device__ __forceinline__ void dn_tap(float k, f3 cp, f3 np, f3 pp, f3 cq, f3 n
     const float w = div_cr(k, ((1.0f + xc) * (1.0f + xn)) * (1.0f + xp));
     sum = sum + w * cq;
     wsum = wsum + w;
-}
-
-__device__ __forceinline__ f3 dn_modulate(f3 c, v4f a, bool divide) {
-    if (a[0] >= kAlbMin) c.x = divide ? div_cr(c.x, a[0]) : c.x * a[0];
-    if (a[1] >= kAlbMin) c.y = divide ? div_cr(c.y, a[1]) : c.y * a[1];
-    if (a[2] >= kAlbMin) c.z = divide ? div_cr(c.z, a[2]) : c.z * a[2];
-    return c;
 }
 
 __global__ __launch_bounds__(256) void k_dn_prologue(const float* __restrict__ rgb, const v4f* __restrict__ alb,
@@ -189,8 +182,6 @@ struct DnvArgs {
     int32_t W, H, s, demodulate;
     float sigma_l, inv_n, inv_p;
 };
-
-__device__ __forceinline__ float lum(f3 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
 
 // One tap q of pixel p: adds w * c_q into sum, w^2 * v_q into vsum and w into wsum.
 __device__ __forceinline__ void dnv_tap(float k, float lp, f3 np, f3 pp, v4f cq4, f3 nq, f3 pq, float rl, float inv_n,
@@ -360,14 +351,8 @@ __global__ __launch_bounds__(kThreads) void k_dnv_level(const DnvArgs A) {
 }
 
 // ---- luminance moments of batch means (pt_moments) ------------------------------
-// pm = (prev.rgb, m1) per pixel, m2 a plane of its own.  One update of one pixel:
-__device__ __forceinline__ void mom_pixel(float r, float g, float b, v4f& pm, float& m2, float bs, bool use_alb, v4f alb) {
-    f3 d = F3(div_cr(r - pm[0], bs), div_cr(g - pm[1], bs), div_cr(b - pm[2], bs));
-    if (use_alb) d = dn_modulate(d, alb, true);
-    const float l = lum(d);
-    pm = v4f{r, g, b, pm[3] + l};
-    m2 = m2 + l * l;
-}
+// pm = (prev.rgb, m1) per pixel, m2 a plane of its own; one update of one pixel is mom_pixel
+// (pt_moments_dev.h).
 
 // QUAD: a lane takes four consecutive pixels, so rgb (3 x 16 B) and m2 (16 B) move as whole 16-byte
 // vectors like pm and alb (rgb must be 16-byte aligned); the npix % 4 last pixels, or every pixel

@@ -60,6 +60,9 @@ int denoise_var_check(const pt_denoise_var_params* p, float samples);
 // pt_moments: the argument checks of pt_moments_update / pt_moments_variance that need no device
 int moments_update_check(const pt_moments* m, float batch_samples);
 int moments_variance_check(const pt_moments* m, float samples);
+// pt_adaptive (pt_adaptive.hip): the argument checks of select and update that need no device
+int adaptive_params_check(const pt_adaptive_params* p);
+int adaptive_update_check(const pt_adaptive* a, float batch_samples);
 // pt_temporal (pt_temporal.hip): the case a frame takes (PT_TEMPORAL_*; < 0: the negated error of its
 // argument checks, no device needed), and the object's own planes a frame of that case writes its
 // G-buffer and albedo to (a producer fills them and passes them to pt_temporal_frame: no copy)

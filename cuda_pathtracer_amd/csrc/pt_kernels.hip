@@ -3429,8 +3429,21 @@ struct pt_ctx {
     float* mom_g = nullptr;
     bool mom_g_valid = false;
     pt_camera scene_cam{};   // the scene camera the context was created with (pt_temporal_frame_ctx)
+    // Adaptive sampling (pt_adaptive_enable): the per-block state, the effective masks
+    // args.cmask points at while enabled (word b = act[b] ? d_cmask[b] : 0), the camera masks and act
+    // on the host (the effective masks' empty share chooses the first bounce's instantiation), and
+    // first-hit planes gA | gB | alb like mom_g.
+    pt_adaptive* ad = nullptr;
+    uint32_t* ad_cmask = nullptr;
+    std::vector<uint32_t> h_cmask;
+    int32_t ad_active = 0;
+    float* ad_g = nullptr;
+    bool ad_g_valid = false;
 
     ~pt_ctx() {
+        if (ad) (void)pt_adaptive_obj_destroy(ad);
+        if (ad_cmask) (void)hipFree(ad_cmask);
+        if (ad_g) (void)hipFree(ad_g);
         if (mom) (void)pt_moments_destroy(mom);
         if (mom_g) (void)hipFree(mom_g);
         g_busy_streams.fetch_sub(busy_streams);
@@ -3520,6 +3533,18 @@ void sync_bounds(pt_ctx* c) {
     c->args.S.room = c->bounds.room;
 }
 
+// The empty-wave first bounce pays when enough of the mask words the kernels read are empty.
+void choose_cmask_skip(pt_ctx* c, size_t empty, size_t nblk) {
+    c->cmask_empty = nblk ? (double)empty / (double)nblk : 0.0;
+    c->cmask_skip = c->cmask_empty >= kSkipEmptyMin;
+    if (const char* sk = std::getenv("PT_AMD_SKIP_EMPTY")) {   // A/B and tests: 0 never, 1 always
+        if (std::strcmp(sk, "0") == 0) c->cmask_skip = false;
+        if (std::strcmp(sk, "1") == 0) c->cmask_skip = true;
+    }
+}
+
+int adaptive_apply(pt_ctx* c);
+
 // First-bounce geom masks (pt::camera_masks), one word per 64 tile pixels.
 int build_cmask(pt_ctx* c) {
     KArgs& A = c->args;
@@ -3547,12 +3572,26 @@ int build_cmask(pt_ctx* c) {
     A.cmask = c->d_cmask;
     size_t empty = 0;
     for (uint32_t m : mask) empty += m == 0u;
-    c->cmask_empty = nblk ? (double)empty / (double)nblk : 0.0;
-    c->cmask_skip = c->cmask_empty >= kSkipEmptyMin;
-    if (const char* sk = std::getenv("PT_AMD_SKIP_EMPTY")) {   // A/B and tests: 0 never, 1 always
-        if (std::strcmp(sk, "0") == 0) c->cmask_skip = false;
-        if (std::strcmp(sk, "1") == 0) c->cmask_skip = true;
+    choose_cmask_skip(c, empty, nblk);
+    c->h_cmask.swap(mask);
+    return c->ad ? adaptive_apply(c) : PT_OK;   // (an adaptive context: act gates the new masks too)
+}
+
+// An adaptive context whose camera masks or act changed, with none of its work queued: the effective
+// masks, their empty share, and the first bounce reads them.
+int adaptive_apply(pt_ctx* c) {
+    const size_t nblk = c->h_cmask.size();
+    if (int rc = pt_adaptive_obj_apply(c->ad, c->d_cmask, c->ad_cmask, c->io_stream)) return rc;
+    std::vector<uint32_t> act(nblk);
+    if (int rc = pt_adaptive_obj_get(c->ad, nullptr, nullptr, nullptr, nullptr, act.data(), nullptr)) return rc;
+    size_t empty = 0, active = 0;
+    for (size_t b = 0; b < nblk; ++b) {
+        empty += act[b] == 0u || c->h_cmask[b] == 0u;
+        active += act[b] != 0u;
     }
+    choose_cmask_skip(c, empty, nblk);
+    c->ad_active = (int32_t)active;
+    c->args.cmask = c->ad_cmask;
     return PT_OK;
 }
 
@@ -4134,6 +4173,8 @@ int pt_destroy(pt_ctx* c) {
 // synchronisation and without rebuilding the masks (pt_ctx_counters counts both).
 int pt_set_flags(pt_ctx* c, const pt_flags* f) {
     if (!c || !f) return pt::fail(PT_ERR_ARG, "null argument");
+    if (c->ad && !c->fused && !f->sort_by_material)
+        return pt::fail(PT_ERR_ARG, "an adaptive context cannot go to the split pipeline (pt_adaptive_enable)");
     auto same = [](float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; };
     const bool lens = !same(f->aperture, c->flags.aperture);
     const bool rays = lens || f->ssaa != c->flags.ssaa || f->dof != c->flags.dof ||
@@ -4491,6 +4532,32 @@ static int rebase_variance(pt_ctx* c, hipStream_t st) {
     return pt_moments_reset(c->mom, c->args.image, st);
 }
 
+// Before an adaptive context's masks change: the first-bounce kernels of its queued passes read them,
+// and a render-ahead iteration traced through the old masks must not be claimed (dropped, as after a
+// flag change).
+static int adaptive_quiesce(pt_ctx* c) {
+    if (int rc = wait_ctx(c)) return rc;
+    if (c->ahead_recorded) {
+        HIP_TRY(hipEventSynchronize(c->ev_ahead));
+        if (c->ahead_valid) {
+            if (int rc = settle_ahead(c, c->io_stream, false)) return rc;
+            HIP_TRY(hipStreamSynchronize(c->io_stream));
+        }
+    }
+    return PT_OK;
+}
+
+// An adaptive context (pt_adaptive_enable) whose accumulator was just cleared on `st`: every block
+// active with no batch, prev = the accumulator; nothing of the context is queued behind the caller's
+// wait, so the masks are rebuilt at once.
+static int adaptive_rebase(pt_ctx* c, hipStream_t st) {
+    c->ad_g_valid = false;
+    if (int rc = pt_adaptive_obj_reset(c->ad, c->args.image, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = adaptive_quiesce(c)) return rc;
+    return adaptive_apply(c);
+}
+
 int pt_preview_rgba(pt_ctx* c, int32_t iter, uint8_t* d_rgba, void* stream) {
     if (!c || !d_rgba || iter <= 0) return pt::fail(PT_ERR_ARG, "bad argument");
     const int npix = c->args.tile.npix;
@@ -4564,6 +4631,7 @@ int pt_stream_destroy(void* stream) {
 // A +0 loaded in place of -0 makes the two agree bit for bit from the first pass on.
 int pt_set_accum(pt_ctx* c, const float* host_rgb) {
     if (!c || !host_rgb) return pt::fail(PT_ERR_ARG, "null argument");
+    if (c->ad) return pt::fail(PT_ERR_ARG, "pt_set_accum on an adaptive context: a saved accumulator carries no per-block counts");
     if (int rc = wait_ctx(c)) return rc;
     const size_t n = (size_t)c->args.tile.npix * 3;
     std::vector<float> img(host_rgb, host_rgb + n);
@@ -4658,6 +4726,8 @@ int pt_reset_image(pt_ctx* c, void* stream) {
     HIP_TRY(hipMemsetAsync(c->args.image, 0, (size_t)c->args.tile.npix * 3 * sizeof(float), (hipStream_t)stream));
     if (c->mom)
         if (int rc = rebase_variance(c, (hipStream_t)stream)) return rc;
+    if (c->ad)
+        if (int rc = adaptive_rebase(c, (hipStream_t)stream)) return rc;
     return mark_ctx(c, (hipStream_t)stream);
 }
 
@@ -4665,6 +4735,7 @@ int pt_reset_image(pt_ctx* c, void* stream) {
 int pt_track_variance(pt_ctx* c, int32_t on) {
     if (!c) return pt::fail(PT_ERR_ARG, "null context");
     if (c->args.tile.world > 1) return pt::fail(PT_ERR_ARG, "variance tracking needs the whole image (world == 1)");
+    if (on && c->ad) return pt::fail(PT_ERR_ARG, "variance tracking on an adaptive context (pt_adaptive_enable keeps its own moments)");
     if (int rc = wait_ctx(c)) return rc;
     if (!on) {
         if (c->mom) (void)pt_moments_destroy(c->mom);
@@ -4767,6 +4838,155 @@ int pt_denoise_image_var(pt_ctx* c, float samples, const pt_denoise_var_params* 
     (void)hipFree(d);
     if (rc) return rc;
     if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_denoise_image_var: ") + hipGetErrorString(e));
+    return PT_OK;
+}
+
+// ---- adaptive sampling ---------------------------------------------------------
+static void adaptive_free(pt_ctx* c) {
+    if (c->ad) (void)pt_adaptive_obj_destroy(c->ad);
+    if (c->ad_cmask) (void)hipFree(c->ad_cmask);
+    if (c->ad_g) (void)hipFree(c->ad_g);
+    c->ad = nullptr;
+    c->ad_cmask = nullptr;
+    c->ad_g = nullptr;
+    c->ad_g_valid = false;
+    c->ad_active = 0;
+}
+
+int pt_adaptive_enable(pt_ctx* c, int32_t on) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    if (!on) {
+        if (!c->ad) return PT_OK;
+        if (int rc = adaptive_quiesce(c)) return rc;
+        adaptive_free(c);
+        size_t empty = 0;
+        for (uint32_t m : c->h_cmask) empty += m == 0u;
+        choose_cmask_skip(c, empty, c->h_cmask.size());
+        c->args.cmask = c->d_cmask;
+        return PT_OK;
+    }
+    if (c->args.tile.world > 1) return pt::fail(PT_ERR_ARG, "adaptive sampling needs the whole image (world == 1)");
+    if (!c->args.cmask)
+        return pt::fail(PT_ERR_ARG, "adaptive sampling needs first-bounce camera masks (an analytic scene of at most 32 "
+                                    "geoms without triangles, PT_AMD_NO_CMASK unset)");
+    if (!c->fused && !c->flags.sort_by_material)
+        return pt::fail(PT_ERR_ARG, "adaptive sampling needs the fused or the material-sorted pipeline (PT_PIPELINE=split "
+                                    "joins the masks of neighbouring blocks)");
+    if (c->args.fl.verify)
+        return pt::fail(PT_ERR_ARG, "adaptive sampling with PT_AMD_VERIFY_BOUNDS=1 (the verifying kernels ignore the masks)");
+    if (c->mom) return pt::fail(PT_ERR_ARG, "adaptive sampling on a context that tracks variance (pt_track_variance)");
+    if (c->ad) return PT_OK;
+    if (int rc = adaptive_quiesce(c)) return rc;
+    const int W = c->args.tile.W;
+    const size_t npix = (size_t)c->args.tile.npix, nblk = c->h_cmask.size();
+    if (int rc = pt_adaptive_obj_create(W, (int32_t)(npix / W), &c->ad)) return rc;
+    if (hipMalloc((void**)&c->ad_cmask, std::max<size_t>(nblk * sizeof(uint32_t), 16)) != hipSuccess ||
+        hipMalloc((void**)&c->ad_g, npix * 12 * sizeof(float)) != hipSuccess) {
+        adaptive_free(c);
+        return pt::fail(PT_ERR_NOMEM, "hipMalloc (adaptive sampling)");
+    }
+    int rc = pt_adaptive_obj_reset(c->ad, c->args.image, c->io_stream);
+    if (!rc) rc = adaptive_apply(c);
+    if (rc) {
+        adaptive_free(c);
+        c->args.cmask = c->d_cmask;
+    }
+    return rc;
+}
+
+int pt_adaptive_update(pt_ctx* c, int32_t demodulate, void* stream) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    if (!c->ad) return pt::fail(PT_ERR_ARG, "adaptive sampling is off (pt_adaptive_enable)");
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = wait_finalize(c, st)) return rc;
+    const size_t npix = (size_t)c->args.tile.npix;
+    if (demodulate && !c->ad_g_valid) {
+        if (int rc = pt_gbuffer(c, c->ad_g, c->ad_g + 4 * npix, c->ad_g + 8 * npix, nullptr, st)) return rc;
+        c->ad_g_valid = true;
+    }
+    if (int rc = pt_adaptive_obj_update(c->ad, c->args.image, (float)c->args.tile.spp, demodulate ? c->ad_g + 8 * npix : nullptr, st))
+        return rc;
+    return mark_ctx(c, st);
+}
+
+int pt_adaptive_select(pt_ctx* c, const pt_adaptive_params* p, int32_t* active_blocks, int32_t* blocks) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    if (!c->ad) return pt::fail(PT_ERR_ARG, "adaptive sampling is off (pt_adaptive_enable)");
+    if (int rc = pt::adaptive_params_check(p)) return rc;
+    if (int rc = adaptive_quiesce(c)) return rc;
+    int32_t n = 0;
+    if (int rc = pt_adaptive_obj_select(c->ad, p, c->io_stream, &n, blocks)) return rc;
+    if (active_blocks) *active_blocks = n;
+    return adaptive_apply(c);
+}
+
+int pt_adaptive_set_mask(pt_ctx* c, const uint8_t* host_mask, int32_t nblocks) {
+    if (!c || !host_mask) return pt::fail(PT_ERR_ARG, "null argument");
+    if (!c->ad) return pt::fail(PT_ERR_ARG, "adaptive sampling is off (pt_adaptive_enable)");
+    if ((size_t)nblocks != c->h_cmask.size() || nblocks < 0)
+        return pt::fail(PT_ERR_ARG, "the mask length differs from the number of blocks");
+    if (int rc = adaptive_quiesce(c)) return rc;
+    if (int rc = pt_adaptive_obj_set_mask(c->ad, host_mask, nblocks, c->io_stream)) return rc;
+    return adaptive_apply(c);
+}
+
+int pt_adaptive_info(const pt_ctx* c, int32_t* on, int32_t* blocks, int32_t* active_blocks, int32_t* updates,
+                     float* batch_samples) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    if (on) *on = c->ad ? 1 : 0;
+    if (blocks) *blocks = 0;
+    if (active_blocks) *active_blocks = c->ad ? c->ad_active : 0;
+    if (updates) *updates = 0;
+    if (batch_samples) *batch_samples = 0.0f;
+    return c->ad ? pt_adaptive_obj_info(c->ad, blocks, updates, batch_samples) : PT_OK;
+}
+
+int pt_adaptive_get(pt_ctx* c, float* h_m1, float* h_m2, float* h_prev_rgb, uint32_t* h_nb, uint32_t* h_act,
+                    uint8_t* h_hot) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    if (!c->ad) return pt::fail(PT_ERR_ARG, "adaptive sampling is off (pt_adaptive_enable)");
+    if (int rc = wait_ctx(c)) return rc;
+    return pt_adaptive_obj_get(c->ad, h_m1, h_m2, h_prev_rgb, h_nb, h_act, h_hot);
+}
+
+// Resolve, the optional variance-guided filter over fresh first-hit planes (samples = 1) and the
+// copies, all on the io stream.
+int pt_adaptive_image(pt_ctx* c, const pt_denoise_var_params* prm, float* host_rgb, float* host_var) {
+    if (!c || (!host_rgb && !host_var)) return pt::fail(PT_ERR_ARG, "null argument");
+    if (!c->ad) return pt::fail(PT_ERR_ARG, "adaptive sampling is off (pt_adaptive_enable)");
+    if (prm)
+        if (int rc = pt::denoise_var_check(prm, 1.0f)) return rc;
+    int32_t updates = 0;
+    (void)pt_adaptive_obj_info(c->ad, nullptr, &updates, nullptr);
+    if (updates < 1) return pt::fail(PT_ERR_ARG, "pt_adaptive_image needs an update (pt_adaptive_update)");
+    const int W = c->args.tile.W;
+    const size_t npix = (size_t)c->args.tile.npix;
+    float* d = nullptr;   // rgb | var | filtered rgb | filtered var
+    if (hipMalloc((void**)&d, npix * 8 * sizeof(float)) != hipSuccess) return pt::fail(PT_ERR_NOMEM, "hipMalloc (adaptive image)");
+    float *d_rgb = d, *d_var = d + 3 * npix, *d_frgb = d + 4 * npix, *d_fvar = d + 7 * npix;
+    pt_denoiser* dn = nullptr;
+    int rc = wait_finalize(c, c->io_stream);
+    if (!rc) rc = pt_adaptive_obj_resolve(c->ad, c->args.image, d_rgb, d_var, c->io_stream);
+    if (!rc && prm) {
+        rc = pt_denoiser_create(W, (int32_t)(npix / W), &dn);
+        if (!rc) rc = pt_gbuffer(c, c->ad_g, c->ad_g + 4 * npix, c->ad_g + 8 * npix, nullptr, c->io_stream);
+        if (!rc) c->ad_g_valid = true;
+        if (!rc) rc = pt_denoiser_run_var(dn, d_rgb, 1.0f, d_var, c->ad_g, c->ad_g + 4 * npix, c->ad_g + 8 * npix, prm, d_frgb,
+                                          d_fvar, c->io_stream);
+    }
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        rc = mark_ctx(c, c->io_stream);
+        if (host_rgb) e = hipMemcpyAsync(host_rgb, prm ? d_frgb : d_rgb, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
+        if (e == hipSuccess && host_var)
+            e = hipMemcpyAsync(host_var, prm ? d_fvar : d_var, npix * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(c->io_stream);
+    if (e == hipSuccess) e = e2;
+    pt_denoiser_destroy(dn);
+    (void)hipFree(d);
+    if (rc) return rc;
+    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_adaptive_image: ") + hipGetErrorString(e));
     return PT_OK;
 }
 

@@ -4,13 +4,19 @@
 // pathtraceFree().  The camera is the first-frame orbit recompute (done by pt_scene_finalize).
 //
 //   pathtracer_amd SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise]
-//                  [--denoise-variance] [--aov DIR]
+//                  [--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K]
 // --denoise also writes the a-trous-filtered image (pt_denoise_image) as ...samp.denoised.png (and
 // .denoised.hdr with --hdr); --denoise-variance tracks the per-pixel variance (pt_track_variance, one
 // pt_variance_update per iteration; the raw image is the same) and writes the variance-guided filter's
 // image (pt_denoise_image_var; the plain filter's with fewer than 2 iterations) as
 // ...samp.denoised-var.png (and .hdr with --hdr); --aov DIR writes the first-hit G-buffer planes
 // (pt_get_gbuffer) as raw little-endian float32 files with a one-line JSON sidecar of their shapes.
+// --adaptive THRESHOLD samples adaptively (pt_adaptive_enable; the other parameters at their defaults):
+// an update after every iteration, a selection of the active 64-pixel blocks every K (default 4)
+// iterations, until no block is active or the iterations are done.  It writes the resolved image
+// (every pixel divided by the samples of its block) as ...samp.adaptive.png instead of the raw one,
+// with --denoise-variance also its variance-filtered version as ...samp.adaptive.denoised-var.png, and
+// reports the samples per block and the segments traced.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -91,19 +97,82 @@ void saveAovs(const Scene& scene, const std::string& dir) {
     std::printf("wrote %s.{gA,gB,albedo,uv}.f32 and %s.aov.json\n", base.c_str(), base.c_str());
 }
 
+// --adaptive: the loop of main() with an update after every iteration and a selection every `every`
+int runAdaptive(const Scene& scene, const char* sceneFile, int total, float threshold, int every, const std::string& out_dir,
+                const std::string& start, bool png, bool hdr, bool denoise_var) {
+    pt_ctx* c = pathtraceContext();
+    pt_adaptive_params prm;
+    pt_adaptive_params_default(&prm);
+    prm.threshold = threshold;
+    auto die = [](const char* what) {
+        std::fprintf(stderr, "error: %s: %s\n", what, pt_last_error());
+        return EXIT_FAILURE;
+    };
+    if (every < 1) {
+        std::fprintf(stderr, "error: --adaptive-every must be >= 1\n");
+        return EXIT_FAILURE;
+    }
+    if (pt_adaptive_enable(c, 1)) return die("adaptive sampling");
+    const auto t0 = std::chrono::steady_clock::now();
+    int iteration = 0;
+    int32_t active = 0, blocks = 0;
+    while (iteration < total) {
+        ++iteration;
+        pathtrace(nullptr, 0, iteration);
+        if (pt_adaptive_update(c, 1, nullptr)) return die("adaptive update");
+        if (iteration % every == 0 && iteration < total) {
+            if (pt_adaptive_select(c, &prm, &active, &blocks)) return die("adaptive select");
+            std::printf("iteration %d: %d of %d blocks active\n", iteration, active, blocks);
+            if (active == 0) break;
+        }
+    }
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    pt_stats_t st{};
+    if (pt_stats(c, &st)) return die("stats");
+    if (pt_adaptive_info(c, nullptr, &blocks, nullptr, nullptr, nullptr)) return die("adaptive info");
+    std::vector<uint32_t> nb((size_t)blocks);
+    if (pt_adaptive_get(c, nullptr, nullptr, nullptr, nb.data(), nullptr, nullptr)) return die("adaptive state");
+    uint32_t lo = nb.empty() ? 0u : nb[0], hi = 0u;
+    double sum = 0.0;
+    for (uint32_t v : nb) {
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+        sum += v;
+    }
+    std::printf("rendered %d iteration(s) of %s (%dx%d, depth %d) adaptively in %.3f s: %llu segments, samples per "
+                "block min %u mean %.2f max %u over %d blocks\n", iteration, sceneFile, scene.state.camera.res[0],
+                scene.state.camera.res[1], scene.state.traceDepth, secs, (unsigned long long)st.segments, lo,
+                blocks ? sum / blocks : 0.0, hi, blocks);
+    std::vector<float> img((size_t)scene.state.camera.res[0] * scene.state.camera.res[1] * 3);
+    if (pt_adaptive_image(c, nullptr, img.data(), nullptr)) return die("adaptive image");
+    if (png) std::printf("wrote %s\n", saveImage(scene, out_dir, start, iteration, false, img.data(), "adaptive").c_str());
+    if (hdr) std::printf("wrote %s\n", saveImage(scene, out_dir, start, iteration, true, img.data(), "adaptive").c_str());
+    if (denoise_var) {
+        pt_denoise_var_params vp;
+        pt_denoise_var_params_default(&vp);
+        if (pt_adaptive_image(c, &vp, img.data(), nullptr)) return die("adaptive denoise");
+        std::printf("wrote %s\n",
+                    saveImage(scene, out_dir, start, iteration, false, img.data(), "adaptive.denoised-var").c_str());
+    }
+    pathtraceFree();
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2) {
         std::printf("Usage: %s SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise] "
-                    "[--denoise-variance] [--aov DIR]\n", argv[0]);
+                    "[--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K]\n", argv[0]);
         return 1;
     }
     const char* sceneFile = argv[1];
     int iterations = -1;
     std::string out_dir, aov_dir;
-    bool sort = false, png = true, hdr = false, denoise = false, denoise_var = false, aov = false;
+    bool sort = false, png = true, hdr = false, denoise = false, denoise_var = false, aov = false, adaptive = false;
+    float adaptive_threshold = 0.0f;
+    int adaptive_every = 4;
     for (int i = 2; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--iterations") && i + 1 < argc) iterations = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out_dir = argv[++i];
@@ -113,6 +182,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
         else if (!std::strcmp(argv[i], "--denoise-variance")) denoise_var = true;
         else if (!std::strcmp(argv[i], "--aov") && i + 1 < argc) { aov_dir = argv[++i]; aov = true; }
+        else if (!std::strcmp(argv[i], "--adaptive") && i + 1 < argc) { adaptive_threshold = (float)std::atof(argv[++i]); adaptive = true; }
+        else if (!std::strcmp(argv[i], "--adaptive-every") && i + 1 < argc) adaptive_every = std::atoi(argv[++i]);
         else {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
             return 1;
@@ -126,6 +197,8 @@ int main(int argc, char** argv) {
     const int total = iterations > 0 ? iterations : (int)scene->state.iterations;
 
     pathtraceInit(scene);
+    if (adaptive) return runAdaptive(*scene, sceneFile, total, adaptive_threshold, adaptive_every, out_dir, startTimeString,
+                                     png, hdr, denoise_var);
     if (denoise_var && pt_track_variance(pathtraceContext(), 1)) {
         std::fprintf(stderr, "error: variance tracking: %s\n", pt_last_error());
         return EXIT_FAILURE;

@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._native import DenoiseParams, DenoiseVarParams, TemporalParams, check_pt, lib  # noqa: F401
+from ._native import AdaptiveParams, DenoiseParams, DenoiseVarParams, TemporalParams, check_pt, lib  # noqa: F401
 
 SPHERE, CUBE, MESH = 0, 1, 2
 
@@ -463,6 +463,60 @@ class PathTracer:
         check_pt(lib().pt_denoise_image_var(self._h, float(samples), C.byref(prm), out.ctypes.data))
         return out
 
+    def adaptive(self, on: bool = True) -> None:
+        """Start (from the accumulator as it stands, every 64-pixel block active) or stop adaptive
+        sampling (pt_adaptive_enable): later passes trace the active blocks only.  Needs
+        world == 1, an analytic scene with camera masks and the fused or the material-sorted pipeline."""
+        check_pt(lib().pt_adaptive_enable(self._h, int(bool(on))))
+
+    def adaptive_update(self, demodulate: bool = True, stream=None) -> None:
+        """One batch (the context's spp) of the active blocks into their moments, after a pass
+        (pt_adaptive_update)."""
+        check_pt(lib().pt_adaptive_update(self._h, int(bool(demodulate)), _stream_ptr(stream)))
+
+    def adaptive_select(self, params: "N.AdaptiveParams | None" = None) -> dict:
+        """Choose the active blocks from the moments (pt_adaptive_select; synchronous):
+        {"active_blocks", "blocks"}; a caller may stop at 0 active blocks."""
+        prm = params if params is not None else N.AdaptiveParams.default()
+        a, n = C.c_int32(), C.c_int32()
+        check_pt(lib().pt_adaptive_select(self._h, C.byref(prm), C.byref(a), C.byref(n)))
+        return {"active_blocks": int(a.value), "blocks": int(n.value)}
+
+    def adaptive_set_mask(self, mask) -> None:
+        """Region rendering: trace only the blocks whose entry is nonzero (pt_adaptive_set_mask; one
+        entry per 64 consecutive pixels of image().reshape(-1, 3))."""
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        check_pt(lib().pt_adaptive_set_mask(self._h, m.ctypes.data, int(m.size)))
+
+    def adaptive_info(self) -> dict:
+        v = [C.c_int32() for _ in range(4)]
+        bs = C.c_float()
+        check_pt(lib().pt_adaptive_info(self._h, *[C.byref(x) for x in v], C.byref(bs)))
+        return {"on": bool(v[0].value), "blocks": int(v[1].value), "active_blocks": int(v[2].value),
+                "updates": int(v[3].value), "batch_samples": float(bs.value)}
+
+    def adaptive_state(self) -> dict:
+        """The adaptive state as it stands (pt_adaptive_get): m1, m2, hot (rows, W), prev (rows, W, 3),
+        nb and act (blocks,) uint32."""
+        r, w = self.rows, self.width
+        nblk = (self.npix + 63) // 64
+        m1, m2 = np.empty((r, w), np.float32), np.empty((r, w), np.float32)
+        pv, hot = np.empty((r, w, 3), np.float32), np.empty((r, w), np.uint8)
+        nb, act = np.empty(nblk, np.uint32), np.empty(nblk, np.uint32)
+        check_pt(lib().pt_adaptive_get(self._h, m1.ctypes.data, m2.ctypes.data, pv.ctypes.data, nb.ctypes.data,
+                                       act.ctypes.data, hot.ctypes.data))
+        return {"m1": m1, "m2": m2, "prev": pv, "nb": nb, "act": act, "hot": hot}
+
+    def adaptive_image(self, var_params: "N.DenoiseVarParams | None" = None, return_variance: bool = False):
+        """(rows, W, 3) float32 per-sample radiance: every pixel's accumulator divided by the samples its
+        block received, or with var_params the variance-guided filter's output on it (pt_adaptive_image).
+        return_variance adds the (rows, W) variance of its luminance."""
+        out = np.empty((self.rows, self.width, 3), np.float32)
+        var = np.empty((self.rows, self.width), np.float32) if return_variance else None
+        check_pt(lib().pt_adaptive_image(self._h, C.byref(var_params) if var_params is not None else None,
+                                         out.ctypes.data, var.ctypes.data if return_variance else None))
+        return (out, var) if return_variance else out
+
     def stats(self) -> dict:
         s = N.Stats()
         check_pt(lib().pt_stats(self._h, C.byref(s)))
@@ -646,18 +700,29 @@ def save_image_hdr(path: str, image: np.ndarray, samples: float) -> str:
 
 
 def render(scene_path: str, iterations: int | None = None, out_dir: str | None = None,
-           gui: GuiDataContainer | None = None, denoise: "bool | str" = False) -> tuple[np.ndarray, str | None]:
+           gui: GuiDataContainer | None = None, denoise: "bool | str" = False,
+           adaptive: "N.AdaptiveParams | bool | None" = None, adaptive_every: int = 4):
     """Headless runCuda loop (main.cpp:114-168): ITERATIONS passes, then saveImage.  denoise=True
     additionally saves FILE.<UTC>.<spp>samp.denoised.png (PathTracer.denoised); the raw PNG is the same.
     denoise="variance" tracks the variance (an update after every pass; the passes and the raw PNG are
     the same) and saves FILE.<UTC>.<spp>samp.denoised-var.png (PathTracer.denoised_variance, or the
-    plain filter when there are fewer than 2 batches)."""
+    plain filter when there are fewer than 2 batches).
+
+    adaptive (AdaptiveParams, or True for the defaults): adaptive sampling — an update
+    after every pass, a selection of the active 64-pixel blocks every `adaptive_every` passes, until no
+    block is active or ITERATIONS passes are done.  Returns (accumulator, path, report) then; report holds
+    the resolved image (accumulator / the samples of the pixel's block), samples_per_block, the
+    active_blocks after every selection, passes and the segments traced.  Saves the resolved image as
+    FILE.<UTC>.<spp>samp.adaptive.png and, with denoise="variance", its variance-filtered version as
+    ....adaptive.denoised-var.png (no raw PNG: the accumulator's pixels hold different sample counts)."""
     if denoise not in (False, True, "variance"):
         raise ValueError(f"denoise must be False, True or 'variance', not {denoise!r}")
     scene = Scene(scene_path)
     st = scene.state()
     iters = iterations if iterations is not None else st.iterations
     pt = PathTracer(scene, gui)
+    if adaptive is not None and adaptive is not False:
+        return _render_adaptive(pt, st, iters, out_dir, denoise, adaptive, adaptive_every)
     if denoise == "variance":
         pt.track_variance(True)
     for it in range(1, iters + 1):
@@ -677,6 +742,39 @@ def render(scene_path: str, iterations: int | None = None, out_dir: str | None =
             save_image(path[:-len(".png")] + ".denoised.png", pt.denoised(iters), 1.0)
     pt.free()
     return img, path
+
+
+def _render_adaptive(pt: PathTracer, st, iters: int, out_dir, denoise, adaptive, every: int):
+    if every < 1:
+        raise ValueError("adaptive_every must be >= 1")
+    if denoise is True:
+        raise ValueError("adaptive rendering filters with denoise='variance' only")
+    prm = N.AdaptiveParams.default() if adaptive is True else adaptive
+    pt.adaptive(True)
+    active, passes = [], 0
+    for it in range(1, iters + 1):
+        pt.render_pass(it)
+        pt.adaptive_update()
+        passes = it
+        if it % every == 0 and it < iters:
+            sel = pt.adaptive_select(prm)
+            active.append(sel["active_blocks"])
+            if sel["active_blocks"] == 0:
+                break
+    img = pt.image()
+    resolved = pt.adaptive_image()
+    state = pt.adaptive_state()
+    report = {"resolved": resolved, "samples_per_block": state["nb"].astype(np.int64) * pt.spp, "active_blocks": active,
+              "passes": passes, "segments": pt.stats()["segments"]}
+    path = None
+    if out_dir is not None:
+        stamp = time.strftime("%Y-%m-%d_%H-%M-%Sz", time.gmtime())
+        path = str(Path(out_dir) / f"{st.imageName}.{stamp}.{passes}samp.adaptive.png")
+        save_image(path, resolved, 1.0)
+        if denoise == "variance":
+            save_image(path[:-len(".png")] + ".denoised-var.png", pt.adaptive_image(N.DenoiseVarParams.default()), 1.0)
+    pt.free()
+    return img, path, report
 
 
 # ---- the reference's global-state API (pathtrace.h:6-9) ------------------------------------

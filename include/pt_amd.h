@@ -538,6 +538,91 @@ int pt_temporal_frame_ctx(pt_temporal* t, pt_ctx* c, float samples, void* stream
 int pt_temporal_image(pt_temporal* t, const pt_denoise_var_params* var_params, float* host_rgb, float* host_var,
                       float* host_h);
 
+/* ---- adaptive sampling and region rendering through active-block masks ------- */
+/* A BLOCK is 64 consecutive pixels in pt_get_image order — one word of the first bounce's camera
+ * masks; the last block may be partial and blocks straddle rows when the width is no multiple of 64.
+ * pt_adaptive needs no context.  Per pixel it keeps pt_moments' planes (prev, m1, m2) and a byte
+ * `hot`; per block nb, the batches the block has received, and act (0 / 1).  Device pointers,
+ * asynchronous on `stream` unless stated (the caller orders the calls of one object); the planes are
+ * allocated at first use, so argument errors (PT_ERR_ARG) are found before any device call.
+ *   reset:    m1 = m2 = 0, nb = 0 and act = 1 everywhere, prev = d_base_rgb (zeros when NULL)
+ *   update:   pt_moments_update on the pixels of the blocks with act == 1, whose nb goes up by one;
+ *             the pixels of the other blocks are not touched and their d_rgb is not read.
+ *             batch_samples as pt_moments_update's
+ *   select:   hot = 1 where nb < min_batches, else hot = e > threshold with
+ *                 mean = m1 / nb, ex2 = m2 / nb, vm = max(0, ex2 - mean * mean) / (nb - 1),
+ *                 e = sqrt(vm) / (mean + floor)        (a NaN is not hot)
+ *             for every pixel, those of inactive blocks too; then act[b] = 1 iff some pixel of b has
+ *             a hot pixel in the (2 dilate + 1)^2 box around it (clipped to the image).  With
+ *             active_blocks / blocks non-NULL the call waits and returns the counts
+ *   set_mask: act[b] = host_mask[b] != 0 for the nblocks == blocks bytes (synchronous)
+ *   apply:    d_cmask_out[b] = act[b] ? d_cmask_in[b] : 0 for every block
+ *   resolve:  d_out_rgb (W*H float3) = d_rgb / (nb * batch_samples), 0 where nb == 0; d_out_var (W*H)
+ *             = pt_moments_variance's expression with the block's nb as the batch count and
+ *             samples = nb * batch_samples, 0 where nb < 2: pt_denoiser_run_var's inputs with
+ *             samples = 1.  Either may be NULL; outputs must not alias d_rgb.  Needs an update
+ *   get:      synchronous, host arrays: m1, m2 (npix), prev (npix * 3), nb, act (blocks, uint32), hot
+ *             (npix bytes); any may be NULL (for tests) */
+typedef struct pt_adaptive_params {
+    float threshold;              /* relative standard error of the pixel's mean luminance; finite, >= 0 */
+    float floor;                  /* added to the mean in e's divisor; finite, > 0 */
+    int32_t min_batches;          /* >= 2: blocks with fewer batches stay active */
+    int32_t dilate;               /* 0..2 */
+    int32_t reserved[4];
+} pt_adaptive_params;
+void pt_adaptive_params_default(pt_adaptive_params* p);
+typedef struct pt_adaptive pt_adaptive;
+int pt_adaptive_obj_create(int32_t width, int32_t height, pt_adaptive** out);
+int pt_adaptive_obj_destroy(pt_adaptive* a);
+int pt_adaptive_obj_info(const pt_adaptive* a, int32_t* blocks, int32_t* updates, float* batch_samples);
+int pt_adaptive_obj_reset(pt_adaptive* a, const float* d_base_rgb, void* stream);
+int pt_adaptive_obj_update(pt_adaptive* a, const float* d_rgb, float batch_samples, const float* d_alb, void* stream);
+int pt_adaptive_obj_select(pt_adaptive* a, const pt_adaptive_params* p, void* stream, int32_t* active_blocks,
+                           int32_t* blocks);
+int pt_adaptive_obj_set_mask(pt_adaptive* a, const uint8_t* host_mask, int32_t nblocks, void* stream);
+int pt_adaptive_obj_apply(pt_adaptive* a, const uint32_t* d_cmask_in, uint32_t* d_cmask_out, void* stream);
+int pt_adaptive_obj_resolve(pt_adaptive* a, const float* d_rgb, float* d_out_rgb, float* d_out_var, void* stream);
+int pt_adaptive_obj_get(pt_adaptive* a, float* h_m1, float* h_m2, float* h_prev_rgb, uint32_t* h_nb, uint32_t* h_act,
+                        uint8_t* h_hot);
+
+/* Adaptive sampling of a context: a pt_adaptive over its accumulator whose act gates the first
+ * bounce.  While enabled the first-bounce kernels read a second mask buffer, word b = act[b] ? the
+ * camera mask of block b : 0; a zero word makes the block's camera rays misses that draw no random
+ * number and store nothing, so the later bounces hold paths of the active blocks only.  Under
+ * rng_key_pixel a pass traced through a mask gives every pixel of an active block the bits of the same
+ * pass traced in full and leaves every other pixel's accumulator as it was.
+ * pt_adaptive_enable(c, 1) needs all of (PT_ERR_ARG otherwise, the message names the condition):
+ *   - world == 1: the object covers the whole image;
+ *   - camera masks (an analytic scene of <= 32 geoms without triangles, PT_AMD_NO_CMASK unset): the
+ *     mesh walk of the first bounce (k_traverse4<FIRST>) reads no mask;
+ *   - the fused or the material-sorted pipeline: the split pipeline (PT_PIPELINE=split) ORs the words
+ *     of up to four blocks per wave, so an inactive block beside an active one would be traced;
+ *   - PT_AMD_VERIFY_BOUNDS off: the verifying kernels compare against a plain per-geom loop that
+ *     ignores the masks;
+ *   - no variance tracking (pt_track_variance; and pt_track_variance(c, 1) is refused while adaptive).
+ * It starts from the accumulator as it stands, every block active with nb = 0; (c, 0) frees everything
+ * and the first bounce reads the camera masks again.
+ * pt_adaptive_update: after a pass (batch = the context's spp), like pt_variance_update.
+ * pt_adaptive_select / pt_adaptive_set_mask change act: synchronous; they wait for the context's queued
+ * work (queued first bounces read the mask), drop unclaimed render-ahead work, rebuild the effective
+ * masks and choose the empty-wave first bounce from them as pt_create does from the camera masks.
+ * pt_set_flags re-applies act when it rebuilds the camera masks; pt_reset_image resets the object (every
+ * block active, nb = 0) and, because that changes the masks, waits for its stream on such a context;
+ * pt_set_accum is refused (a saved accumulator carries no per-block counts).  pt_stats' bounce_live[0]
+ * still counts every pixel.  pt_preview_rgba divides by one count and is not adaptive-aware.
+ * pt_adaptive_image: resolve, then with var_params pt_denoiser_run_var (samples = 1) over a fresh
+ * first-hit G-buffer; host_rgb (npix float3), host_var (npix, the filtered variance with var_params);
+ * either may be NULL, not both.  Synchronous. */
+int pt_adaptive_enable(pt_ctx* c, int32_t on);
+int pt_adaptive_update(pt_ctx* c, int32_t demodulate, void* stream);
+int pt_adaptive_select(pt_ctx* c, const pt_adaptive_params* p, int32_t* active_blocks, int32_t* blocks);
+int pt_adaptive_set_mask(pt_ctx* c, const uint8_t* host_mask, int32_t nblocks);
+int pt_adaptive_info(const pt_ctx* c, int32_t* on, int32_t* blocks, int32_t* active_blocks, int32_t* updates,
+                     float* batch_samples);
+int pt_adaptive_get(pt_ctx* c, float* h_m1, float* h_m2, float* h_prev_rgb, uint32_t* h_nb, uint32_t* h_act,
+                    uint8_t* h_hot);
+int pt_adaptive_image(pt_ctx* c, const pt_denoise_var_params* var_params, float* host_rgb, float* host_var);
+
 #ifdef __cplusplus
 }
 #endif
