@@ -33,7 +33,8 @@ DEVICE_SRCS = ["sc_kernels.hip", "sc_variants.hip", "pt_kernels.hip", "bvh_build
 # register pairs and moves: k_bounce took 79 VGPRs (6 waves/SIMD) instead of 60 (8 waves), and
 # measured 30.8k vs 32.7k Mray/s on the bench (same box, alternating runs; same bits).
 EXTRA = {"pt_kernels.hip": ["-fno-slp-vectorize"]}
-HOST_SRCS = ["pt_scene.cpp", "pt_mesh.cpp", "pt_image.cpp", "pt_jpeg.cpp", "pt_bounds.cpp", "pt_bvh_layout.cpp"]
+HOST_SRCS = ["pt_scene.cpp", "pt_mesh.cpp", "pt_image.cpp", "pt_jpeg.cpp", "pt_bounds.cpp", "pt_bvh_layout.cpp",
+             "pt_ctx_image.cpp"]
 
 
 def other_objs(without: str) -> list[Path]:

@@ -1,4 +1,4 @@
-// Internal host-side types shared by the scene loader, mesh/BVH builder and render context.
+// Internal host-side types and checks shared by the scene loader, mesh/BVH builder, image-level objects and render context.
 #pragma once
 #include <cstdint>
 #include <cstring>

@@ -36,6 +36,7 @@
 #include "lookback.h"
 #include "pt_device.h"
 #include "pt_internal.h"
+#include "pt_ctx.h"
 #include "../../include/sc_amd.h"
 
 using namespace ptd;
@@ -3295,13 +3296,6 @@ __global__ void k_selftest_math(uint64_t n, uint32_t seed, unsigned long long* b
 // ------------------------------------------------------------------------------------------
 // Host context
 // ------------------------------------------------------------------------------------------
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess)                                                               \
-            return pt::fail(PT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 struct ProfEv {
     hipEvent_t a, b;
     int kind;
@@ -3318,7 +3312,7 @@ static int stream_budget() {
     return n > 0 ? n : 4;
 }
 
-struct pt_ctx {
+struct pt_ctx : pt::CtxHead {   // (the head: the image, the context's synchronisation, the image-level features)
     int device = 0;
     int depth = 8;
     int nmats = 0;
@@ -3390,19 +3384,9 @@ struct pt_ctx {
     bool trav_quads = false;             // mesh mode 2 walks the 4-wide layout (PT_AMD_TRAV=pairs: off)
     int walk_k = kT4K;                   // k_traverse4's triangle tasks per lane: kT4K, 1 with the exact t-cull
     hipStream_t fin_stream = nullptr;
-    hipEvent_t ev_pass[2] = {}, ev_fin[2] = {};
+    hipEvent_t ev_pass[2] = {};
     bool fin_out[2] = {false, false};
-    int col_half = 0, last_fin = -1;
-    // Context-scoped synchronisation (no hipDeviceSynchronize, no synchronous copy on the legacy
-    // default stream): ev_done is recorded after the last work this context enqueued (a pass ends
-    // with it on the stream that finishes the pass: the caller's, or the finalize stream, which the
-    // lanes join); the synchronous entry points wait for that event alone and move data on io_stream,
-    // a non-blocking stream of their own.  So reading one context's image does not wait for another
-    // context's passes, nor for unrelated work elsewhere on the GPU.
-    hipStream_t io_stream = nullptr;
-    hipEvent_t ev_done = nullptr;
-    bool done_recorded = false;
-    hipStream_t done_stream = nullptr;   // the stream ev_done was last recorded on
+    int col_half = 0;
     int busy_streams = 0;                // compute streams this context holds (stream budget, below)
     bool lanes_capped = false;           // pt_create gave it fewer lanes than it would alone
     hipStream_t pass_stream = nullptr;   // the caller's stream of the last pass or render-ahead
@@ -3422,30 +3406,10 @@ struct pt_ctx {
     pt_flags ahead_flags{};
     uint8_t* colflag = nullptr;   // 2 x P flag bytes (KArgs::colflag), pass halves like colbuf; zero between passes
     uint8_t* ahead_flag = nullptr;   // npix flag bytes of the render-ahead colours
-    // Variance tracking (pt_track_variance, world == 1): luminance moments of the accumulator's batch
-    // means, and the first-hit planes gA | gB | alb (12 floats per pixel) whose albedo demodulates them.
-    // The planes are filled at the first update after tracking starts or the accumulator is rebased.
-    pt_moments* mom = nullptr;
-    float* mom_g = nullptr;
-    bool mom_g_valid = false;
-    pt_camera scene_cam{};   // the scene camera the context was created with (pt_temporal_frame_ctx)
-    // Adaptive sampling (pt_adaptive_enable): the per-block state, the effective masks
-    // args.cmask points at while enabled (word b = act[b] ? d_cmask[b] : 0), the camera masks and act
-    // on the host (the effective masks' empty share chooses the first bounce's instantiation), and
-    // first-hit planes gA | gB | alb like mom_g.
-    pt_adaptive* ad = nullptr;
-    uint32_t* ad_cmask = nullptr;
-    std::vector<uint32_t> h_cmask;
-    int32_t ad_active = 0;
-    float* ad_g = nullptr;
-    bool ad_g_valid = false;
+    std::vector<uint32_t> h_cmask;   // d_cmask on the host (an adaptive context gates it by act: pt::point_cmask)
 
     ~pt_ctx() {
-        if (ad) (void)pt_adaptive_obj_destroy(ad);
-        if (ad_cmask) (void)hipFree(ad_cmask);
-        if (ad_g) (void)hipFree(ad_g);
-        if (mom) (void)pt_moments_destroy(mom);
-        if (mom_g) (void)hipFree(mom_g);
+        release();
         g_busy_streams.fetch_sub(busy_streams);
         for (auto& e : events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
         for (int h = 0; h < 2; ++h) {
@@ -3477,33 +3441,7 @@ struct pt_ctx {
 
 namespace {
 
-// Synchronous copy on the context's own non-blocking stream (pt_ctx::io_stream): unlike hipMemcpy,
-// which runs on the legacy default stream, it waits for nothing but itself.
-hipError_t io_copy(pt_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-    if (!c->io_stream) return hipMemcpy(dst, src, bytes, kind);   // (pt_create, before the stream exists)
-    hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, c->io_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->io_stream);
-    return e;
-}
-
-// Wait for everything this context has enqueued so far (pt_ctx::ev_done).
-int wait_ctx(pt_ctx* c) {
-    if (c->done_recorded) HIP_TRY(hipEventSynchronize(c->ev_done));
-    return PT_OK;
-}
-int mark_ctx(pt_ctx* c, hipStream_t s) {
-    HIP_TRY(hipEventRecord(c->ev_done, s));
-    c->done_recorded = true;
-    c->done_stream = s;
-    return PT_OK;
-}
-// Work about to be queued on st that shares the context's path buffers, control words or ahead
-// buffers waits for everything the context queued before, when that went to another stream (on
-// the same stream, stream order already holds).
-int order_after_ctx(pt_ctx* c, hipStream_t st) {
-    if (c->done_recorded && c->done_stream != st) HIP_TRY(hipStreamWaitEvent(st, c->ev_done, 0));
-    return PT_OK;
-}
+using pt::io_copy, pt::wait_ctx, pt::mark_ctx, pt::order_after_ctx, pt::wait_finalize;
 
 void set_flags_dev(pt_ctx* c, const pt_flags& f) {
     c->flags = f;
@@ -3543,8 +3481,6 @@ void choose_cmask_skip(pt_ctx* c, size_t empty, size_t nblk) {
     }
 }
 
-int adaptive_apply(pt_ctx* c);
-
 // First-bounce geom masks (pt::camera_masks), one word per 64 tile pixels.
 int build_cmask(pt_ctx* c) {
     KArgs& A = c->args;
@@ -3569,30 +3505,9 @@ int build_cmask(pt_ctx* c) {
     }
     hipError_t e = io_copy(c, c->d_cmask, mask.data(), nblk * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("camera masks: ") + hipGetErrorString(e));
-    A.cmask = c->d_cmask;
-    size_t empty = 0;
-    for (uint32_t m : mask) empty += m == 0u;
-    choose_cmask_skip(c, empty, nblk);
     c->h_cmask.swap(mask);
-    return c->ad ? adaptive_apply(c) : PT_OK;   // (an adaptive context: act gates the new masks too)
-}
-
-// An adaptive context whose camera masks or act changed, with none of its work queued: the effective
-// masks, their empty share, and the first bounce reads them.
-int adaptive_apply(pt_ctx* c) {
-    const size_t nblk = c->h_cmask.size();
-    if (int rc = pt_adaptive_obj_apply(c->ad, c->d_cmask, c->ad_cmask, c->io_stream)) return rc;
-    std::vector<uint32_t> act(nblk);
-    if (int rc = pt_adaptive_obj_get(c->ad, nullptr, nullptr, nullptr, nullptr, act.data(), nullptr)) return rc;
-    size_t empty = 0, active = 0;
-    for (size_t b = 0; b < nblk; ++b) {
-        empty += act[b] == 0u || c->h_cmask[b] == 0u;
-        active += act[b] != 0u;
-    }
-    choose_cmask_skip(c, empty, nblk);
-    c->ad_active = (int32_t)active;
-    c->args.cmask = c->ad_cmask;
-    return PT_OK;
+    pt::point_cmask(c, nullptr, nullptr);
+    return c->ad ? pt::adaptive_apply(c) : PT_OK;   // (an adaptive context: act gates the new masks too)
 }
 
 // One block of 4P planes per parity: the fused / split pipelines use the first three as the
@@ -4030,6 +3945,11 @@ int pt_create(const pt_scene* scene, const pt_flags* flags, const pt_shard* shar
         if (const char* rf = std::getenv("PT_AMD_REFILL")) A.refill_min = std::max(1, std::min(64, std::atoi(rf)));
     }
     if (int rc = c->alloc(&A.image, (size_t)npix * 3)) return bail(rc);
+    c->image = A.image;   // (the head's description of the image: written here only)
+    c->npix = (size_t)npix;
+    c->W = W;
+    c->world = sh.world;
+    c->spp = sh.spp;
     if ((e = hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming)) != hipSuccess)
         return bail(pt::fail(PT_ERR_HIP, std::string("context event: ") + hipGetErrorString(e)));
     if (sh.spp > 1) {
@@ -4244,8 +4164,6 @@ int pt_ctx_counters(const pt_ctx* c, uint64_t* mask_builds, uint64_t* flag_syncs
     if (flag_syncs) *flag_syncs = c->n_flag_syncs;
     return PT_OK;
 }
-
-static int wait_finalize(pt_ctx* c, hipStream_t st);
 
 // One pass on st; ahead: a render-ahead pass (one-iteration context) whose colours and counts go to
 // the ahead buffers and that neither finalizes nor marks the context (pt_render_ahead).
@@ -4516,48 +4434,6 @@ static int render_ahead(pt_ctx* c, int32_t iter, hipStream_t st) {
     return PT_OK;
 }
 
-// Work on `st` that reads or writes the image first waits for this context's last enqueued work
-// (the last deferred finalize of a batched pass, or an image call on another stream), and is then
-// itself the work the synchronous entry points wait for (mark_ctx).
-static int wait_finalize(pt_ctx* c, hipStream_t st) {
-    if (c->done_recorded) HIP_TRY(hipStreamWaitEvent(st, c->ev_done, 0));
-    else if (c->last_fin >= 0) HIP_TRY(hipStreamWaitEvent(st, c->ev_fin[c->last_fin], 0));
-    return PT_OK;
-}
-
-// A tracking context (pt_track_variance) whose accumulator was just replaced on `st`: the moments
-// start again from it.
-static int rebase_variance(pt_ctx* c, hipStream_t st) {
-    c->mom_g_valid = false;
-    return pt_moments_reset(c->mom, c->args.image, st);
-}
-
-// Before an adaptive context's masks change: the first-bounce kernels of its queued passes read them,
-// and a render-ahead iteration traced through the old masks must not be claimed (dropped, as after a
-// flag change).
-static int adaptive_quiesce(pt_ctx* c) {
-    if (int rc = wait_ctx(c)) return rc;
-    if (c->ahead_recorded) {
-        HIP_TRY(hipEventSynchronize(c->ev_ahead));
-        if (c->ahead_valid) {
-            if (int rc = settle_ahead(c, c->io_stream, false)) return rc;
-            HIP_TRY(hipStreamSynchronize(c->io_stream));
-        }
-    }
-    return PT_OK;
-}
-
-// An adaptive context (pt_adaptive_enable) whose accumulator was just cleared on `st`: every block
-// active with no batch, prev = the accumulator; nothing of the context is queued behind the caller's
-// wait, so the masks are rebuilt at once.
-static int adaptive_rebase(pt_ctx* c, hipStream_t st) {
-    c->ad_g_valid = false;
-    if (int rc = pt_adaptive_obj_reset(c->ad, c->args.image, st)) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int rc = adaptive_quiesce(c)) return rc;
-    return adaptive_apply(c);
-}
-
 int pt_preview_rgba(pt_ctx* c, int32_t iter, uint8_t* d_rgba, void* stream) {
     if (!c || !d_rgba || iter <= 0) return pt::fail(PT_ERR_ARG, "bad argument");
     const int npix = c->args.tile.npix;
@@ -4585,74 +4461,6 @@ int pt_tile_info(const pt_ctx* c, int32_t* width, int32_t* rows, int32_t* npix, 
     return PT_OK;
 }
 
-int pt_get_image(pt_ctx* c, float* host_rgb) {
-    if (!c || !host_rgb) return pt::fail(PT_ERR_ARG, "null argument");
-    if (int rc = wait_ctx(c)) return rc;   // this context's passes only (pathtrace.cu:524's copy)
-    HIP_TRY(io_copy(c, host_rgb, c->args.image, (size_t)c->args.tile.npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return PT_OK;
-}
-
-int pt_get_accum(pt_ctx* c, float* host_rgb) { return pt_get_image(c, host_rgb); }
-
-int pt_host_register(void* host, uint64_t bytes) {
-    if (!host || !bytes) return pt::fail(PT_ERR_ARG, "null argument");
-    const hipError_t e = hipHostRegister(host, (size_t)bytes, hipHostRegisterDefault);
-    if (e != hipSuccess) {
-        // a caller may go on without the page lock (the copies still work, staged): leave no sticky
-        // last-error behind for the next launch's hipGetLastError check to report
-        (void)hipGetLastError();
-        return pt::fail(PT_ERR_DEVICE, std::string("hipHostRegister: ") + hipGetErrorString(e));
-    }
-    return PT_OK;
-}
-
-int pt_host_unregister(void* host) {
-    if (!host) return pt::fail(PT_ERR_ARG, "null argument");
-    HIP_TRY(hipHostUnregister(host));
-    return PT_OK;
-}
-
-int pt_stream_create(void** stream) {
-    if (!stream) return pt::fail(PT_ERR_ARG, "null argument");
-    hipStream_t s = nullptr;
-    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    *stream = s;
-    return PT_OK;
-}
-
-int pt_stream_destroy(void* stream) {
-    if (stream) HIP_TRY(hipStreamDestroy((hipStream_t)stream));
-    return PT_OK;
-}
-
-// The accumulator is loaded with every -0 replaced by +0.  The reference adds every iteration's colour
-// (zero or not) into every pixel, so after any pass its image holds no -0 (-0 + 0 = +0); the passes here
-// skip the additions of zero colours (retire, k_finalize_spp), which are identities on every value but -0.
-// A +0 loaded in place of -0 makes the two agree bit for bit from the first pass on.
-int pt_set_accum(pt_ctx* c, const float* host_rgb) {
-    if (!c || !host_rgb) return pt::fail(PT_ERR_ARG, "null argument");
-    if (c->ad) return pt::fail(PT_ERR_ARG, "pt_set_accum on an adaptive context: a saved accumulator carries no per-block counts");
-    if (int rc = wait_ctx(c)) return rc;
-    const size_t n = (size_t)c->args.tile.npix * 3;
-    std::vector<float> img(host_rgb, host_rgb + n);
-    for (float& v : img)
-        if (v == 0.0f) v = 0.0f;   // (-0 == 0: both zeros become +0)
-    HIP_TRY(io_copy(c, c->args.image, img.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    if (c->mom) {
-        if (int rc = rebase_variance(c, c->io_stream)) return rc;
-        return mark_ctx(c, c->io_stream);
-    }
-    return PT_OK;
-}
-
-int pt_copy_image(pt_ctx* c, float* d_rgb, void* stream) {
-    if (!c || !d_rgb) return pt::fail(PT_ERR_ARG, "null argument");
-    if (int rc = wait_finalize(c, (hipStream_t)stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(d_rgb, c->args.image, (size_t)c->args.tile.npix * 3 * sizeof(float),
-                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return mark_ctx(c, (hipStream_t)stream);
-}
-
 // The first-hit feature planes of the tile (k_gbuffer), ordered like pt_copy_image: after the context's
 // queued work (a pt_set_flags in between has synchronised by itself), and marked as its last work.
 int pt_gbuffer(pt_ctx* c, float* d_gA, float* d_gB, float* d_alb, float* d_uv, void* stream) {
@@ -4668,350 +4476,6 @@ int pt_gbuffer(pt_ctx* c, float* d_gA, float* d_gB, float* d_alb, float* d_uv, v
     auto kern = A.S.ntris > 0 ? k_gbuffer<true> : k_gbuffer<false>;
     hipLaunchKernelGGL(kern, grid, dim3(kBlock), 0, st, A, (v4f*)d_gA, (v4f*)d_gB, (v4f*)d_alb, (v2f*)d_uv);
     HIP_TRY(hipGetLastError());
-    return mark_ctx(c, st);
-}
-
-int pt_get_gbuffer(pt_ctx* c, float* h_gA, float* h_gB, float* h_alb, float* h_uv) {
-    if (!c || !h_gA || !h_gB || !h_alb) return pt::fail(PT_ERR_ARG, "null argument");
-    const size_t npix = (size_t)c->args.tile.npix;
-    float* d = nullptr;   // gA | gB | alb | uv
-    if (hipMalloc((void**)&d, npix * 14 * sizeof(float)) != hipSuccess) return pt::fail(PT_ERR_NOMEM, "hipMalloc (G-buffer)");
-    int rc = pt_gbuffer(c, d, d + 4 * npix, d + 8 * npix, h_uv ? d + 12 * npix : nullptr, c->io_stream);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        float* dst[4] = {h_gA, h_gB, h_alb, h_uv};
-        const size_t off[5] = {0, 4 * npix, 8 * npix, 12 * npix, 14 * npix};
-        for (int k = 0; k < 4 && e == hipSuccess; ++k)
-            if (dst[k]) e = hipMemcpyAsync(dst[k], d + off[k], (off[k + 1] - off[k]) * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
-        const hipError_t e2 = hipStreamSynchronize(c->io_stream);
-        if (e == hipSuccess) e = e2;
-    }
-    (void)hipFree(d);
-    if (rc) return rc;
-    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_get_gbuffer: ") + hipGetErrorString(e));
-    return PT_OK;
-}
-
-// G-buffer + accumulator -> denoised host image: everything on the context's io stream, the filter
-// reading the accumulator in place (it is not modified).
-int pt_denoise_image(pt_ctx* c, float samples, const pt_denoise_params* prm, float* host_out_rgb) {
-    if (!c || !host_out_rgb) return pt::fail(PT_ERR_ARG, "null argument");
-    if (c->args.tile.world > 1) return pt::fail(PT_ERR_ARG, "pt_denoise_image needs the whole image (world == 1)");
-    if (int rc = pt::denoise_check(prm, samples)) return rc;
-    const int W = c->args.tile.W;
-    const size_t npix = (size_t)c->args.tile.npix;
-    float* d = nullptr;   // gA | gB | alb | out
-    if (hipMalloc((void**)&d, npix * 15 * sizeof(float)) != hipSuccess) return pt::fail(PT_ERR_NOMEM, "hipMalloc (denoise)");
-    pt_denoiser* dn = nullptr;
-    int rc = pt_denoiser_create(W, (int32_t)(npix / W), &dn);
-    if (!rc) rc = pt_gbuffer(c, d, d + 4 * npix, d + 8 * npix, nullptr, c->io_stream);
-    if (!rc) rc = pt_denoiser_run(dn, c->args.image, samples, d, d + 4 * npix, d + 8 * npix, prm, d + 12 * npix, c->io_stream);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        rc = mark_ctx(c, c->io_stream);
-        e = hipMemcpyAsync(host_out_rgb, d + 12 * npix, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
-    }
-    const hipError_t e2 = hipStreamSynchronize(c->io_stream);
-    if (e == hipSuccess) e = e2;
-    pt_denoiser_destroy(dn);
-    (void)hipFree(d);
-    if (rc) return rc;
-    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_denoise_image: ") + hipGetErrorString(e));
-    return PT_OK;
-}
-
-int pt_reset_image(pt_ctx* c, void* stream) {
-    if (!c) return pt::fail(PT_ERR_ARG, "null context");
-    if (int rc = wait_finalize(c, (hipStream_t)stream)) return rc;
-    HIP_TRY(hipMemsetAsync(c->args.image, 0, (size_t)c->args.tile.npix * 3 * sizeof(float), (hipStream_t)stream));
-    if (c->mom)
-        if (int rc = rebase_variance(c, (hipStream_t)stream)) return rc;
-    if (c->ad)
-        if (int rc = adaptive_rebase(c, (hipStream_t)stream)) return rc;
-    return mark_ctx(c, (hipStream_t)stream);
-}
-
-// ---- variance tracking ---------------------------------------------------------
-int pt_track_variance(pt_ctx* c, int32_t on) {
-    if (!c) return pt::fail(PT_ERR_ARG, "null context");
-    if (c->args.tile.world > 1) return pt::fail(PT_ERR_ARG, "variance tracking needs the whole image (world == 1)");
-    if (on && c->ad) return pt::fail(PT_ERR_ARG, "variance tracking on an adaptive context (pt_adaptive_enable keeps its own moments)");
-    if (int rc = wait_ctx(c)) return rc;
-    if (!on) {
-        if (c->mom) (void)pt_moments_destroy(c->mom);
-        if (c->mom_g) (void)hipFree(c->mom_g);
-        c->mom = nullptr;
-        c->mom_g = nullptr;
-        c->mom_g_valid = false;
-        return PT_OK;
-    }
-    if (c->mom) return PT_OK;
-    const int W = c->args.tile.W;
-    const size_t npix = (size_t)c->args.tile.npix;
-    if (int rc = pt_moments_create(W, (int32_t)(npix / W), &c->mom)) return rc;
-    if (hipMalloc((void**)&c->mom_g, npix * 12 * sizeof(float)) != hipSuccess) {
-        (void)pt_moments_destroy(c->mom);
-        c->mom = nullptr;
-        return pt::fail(PT_ERR_NOMEM, "hipMalloc (variance tracking)");
-    }
-    if (int rc = rebase_variance(c, c->io_stream)) return rc;
-    return mark_ctx(c, c->io_stream);
-}
-
-// The context's first-hit planes for variance tracking, on st (pt_gbuffer orders and marks itself).
-static int variance_planes(pt_ctx* c, hipStream_t st) {
-    const size_t npix = (size_t)c->args.tile.npix;
-    if (int rc = pt_gbuffer(c, c->mom_g, c->mom_g + 4 * npix, c->mom_g + 8 * npix, nullptr, st)) return rc;
-    c->mom_g_valid = true;
-    return PT_OK;
-}
-
-int pt_variance_update(pt_ctx* c, float batch_samples, int32_t demodulate, void* stream) {
-    if (!c) return pt::fail(PT_ERR_ARG, "null context");
-    if (!c->mom) return pt::fail(PT_ERR_ARG, "variance tracking is off (pt_track_variance)");
-    if (int rc = pt::moments_update_check(c->mom, batch_samples)) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    if (int rc = wait_finalize(c, st)) return rc;
-    if (demodulate && !c->mom_g_valid)
-        if (int rc = variance_planes(c, st)) return rc;
-    const float* alb = demodulate ? c->mom_g + 8 * (size_t)c->args.tile.npix : nullptr;
-    if (int rc = pt_moments_update(c->mom, c->args.image, batch_samples, alb, st)) return rc;
-    return mark_ctx(c, st);
-}
-
-int pt_variance_info(const pt_ctx* c, int32_t* on, int32_t* batches, float* batch_samples) {
-    if (!c) return pt::fail(PT_ERR_ARG, "null context");
-    if (on) *on = c->mom ? 1 : 0;
-    if (batches) *batches = 0;
-    if (batch_samples) *batch_samples = 0.0f;
-    return c->mom ? pt_moments_info(c->mom, batches, batch_samples) : PT_OK;
-}
-
-int pt_get_variance(pt_ctx* c, float samples, float* host_var) {
-    if (!c || !host_var) return pt::fail(PT_ERR_ARG, "null argument");
-    if (!c->mom) return pt::fail(PT_ERR_ARG, "variance tracking is off (pt_track_variance)");
-    if (int rc = pt::moments_variance_check(c->mom, samples)) return rc;
-    const size_t npix = (size_t)c->args.tile.npix;
-    float* d = nullptr;
-    if (hipMalloc((void**)&d, npix * sizeof(float)) != hipSuccess) return pt::fail(PT_ERR_NOMEM, "hipMalloc (variance)");
-    int rc = wait_finalize(c, c->io_stream);
-    if (!rc) rc = pt_moments_variance(c->mom, samples, d, c->io_stream);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        rc = mark_ctx(c, c->io_stream);
-        e = hipMemcpyAsync(host_var, d, npix * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
-    }
-    const hipError_t e2 = hipStreamSynchronize(c->io_stream);
-    if (e == hipSuccess) e = e2;
-    (void)hipFree(d);
-    if (rc) return rc;
-    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_get_variance: ") + hipGetErrorString(e));
-    return PT_OK;
-}
-
-// Like pt_denoise_image, with the tracked variance: fresh first-hit planes (into the context's own),
-// the variance of `samples` samples, the filter and the copy, all on the io stream.
-int pt_denoise_image_var(pt_ctx* c, float samples, const pt_denoise_var_params* prm, float* host_out_rgb) {
-    if (!c || !host_out_rgb) return pt::fail(PT_ERR_ARG, "null argument");
-    if (c->args.tile.world > 1) return pt::fail(PT_ERR_ARG, "pt_denoise_image_var needs the whole image (world == 1)");
-    if (!c->mom) return pt::fail(PT_ERR_ARG, "variance tracking is off (pt_track_variance)");
-    if (int rc = pt::denoise_var_check(prm, samples)) return rc;
-    if (int rc = pt::moments_variance_check(c->mom, samples)) return rc;
-    const int W = c->args.tile.W;
-    const size_t npix = (size_t)c->args.tile.npix;
-    float* d = nullptr;   // var | out
-    if (hipMalloc((void**)&d, npix * 4 * sizeof(float)) != hipSuccess) return pt::fail(PT_ERR_NOMEM, "hipMalloc (denoise)");
-    pt_denoiser* dn = nullptr;
-    int rc = pt_denoiser_create(W, (int32_t)(npix / W), &dn);
-    if (!rc) rc = variance_planes(c, c->io_stream);
-    if (!rc) rc = pt_moments_variance(c->mom, samples, d, c->io_stream);
-    if (!rc) rc = pt_denoiser_run_var(dn, c->args.image, samples, d, c->mom_g, c->mom_g + 4 * npix, c->mom_g + 8 * npix, prm,
-                                      d + npix, nullptr, c->io_stream);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        rc = mark_ctx(c, c->io_stream);
-        e = hipMemcpyAsync(host_out_rgb, d + npix, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
-    }
-    const hipError_t e2 = hipStreamSynchronize(c->io_stream);
-    if (e == hipSuccess) e = e2;
-    pt_denoiser_destroy(dn);
-    (void)hipFree(d);
-    if (rc) return rc;
-    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_denoise_image_var: ") + hipGetErrorString(e));
-    return PT_OK;
-}
-
-// ---- adaptive sampling ---------------------------------------------------------
-static void adaptive_free(pt_ctx* c) {
-    if (c->ad) (void)pt_adaptive_obj_destroy(c->ad);
-    if (c->ad_cmask) (void)hipFree(c->ad_cmask);
-    if (c->ad_g) (void)hipFree(c->ad_g);
-    c->ad = nullptr;
-    c->ad_cmask = nullptr;
-    c->ad_g = nullptr;
-    c->ad_g_valid = false;
-    c->ad_active = 0;
-}
-
-int pt_adaptive_enable(pt_ctx* c, int32_t on) {
-    if (!c) return pt::fail(PT_ERR_ARG, "null context");
-    if (!on) {
-        if (!c->ad) return PT_OK;
-        if (int rc = adaptive_quiesce(c)) return rc;
-        adaptive_free(c);
-        size_t empty = 0;
-        for (uint32_t m : c->h_cmask) empty += m == 0u;
-        choose_cmask_skip(c, empty, c->h_cmask.size());
-        c->args.cmask = c->d_cmask;
-        return PT_OK;
-    }
-    if (c->args.tile.world > 1) return pt::fail(PT_ERR_ARG, "adaptive sampling needs the whole image (world == 1)");
-    if (!c->args.cmask)
-        return pt::fail(PT_ERR_ARG, "adaptive sampling needs first-bounce camera masks (an analytic scene of at most 32 "
-                                    "geoms without triangles, PT_AMD_NO_CMASK unset)");
-    if (!c->fused && !c->flags.sort_by_material)
-        return pt::fail(PT_ERR_ARG, "adaptive sampling needs the fused or the material-sorted pipeline (PT_PIPELINE=split "
-                                    "joins the masks of neighbouring blocks)");
-    if (c->args.fl.verify)
-        return pt::fail(PT_ERR_ARG, "adaptive sampling with PT_AMD_VERIFY_BOUNDS=1 (the verifying kernels ignore the masks)");
-    if (c->mom) return pt::fail(PT_ERR_ARG, "adaptive sampling on a context that tracks variance (pt_track_variance)");
-    if (c->ad) return PT_OK;
-    if (int rc = adaptive_quiesce(c)) return rc;
-    const int W = c->args.tile.W;
-    const size_t npix = (size_t)c->args.tile.npix, nblk = c->h_cmask.size();
-    if (int rc = pt_adaptive_obj_create(W, (int32_t)(npix / W), &c->ad)) return rc;
-    if (hipMalloc((void**)&c->ad_cmask, std::max<size_t>(nblk * sizeof(uint32_t), 16)) != hipSuccess ||
-        hipMalloc((void**)&c->ad_g, npix * 12 * sizeof(float)) != hipSuccess) {
-        adaptive_free(c);
-        return pt::fail(PT_ERR_NOMEM, "hipMalloc (adaptive sampling)");
-    }
-    int rc = pt_adaptive_obj_reset(c->ad, c->args.image, c->io_stream);
-    if (!rc) rc = adaptive_apply(c);
-    if (rc) {
-        adaptive_free(c);
-        c->args.cmask = c->d_cmask;
-    }
-    return rc;
-}
-
-int pt_adaptive_update(pt_ctx* c, int32_t demodulate, void* stream) {
-    if (!c) return pt::fail(PT_ERR_ARG, "null context");
-    if (!c->ad) return pt::fail(PT_ERR_ARG, "adaptive sampling is off (pt_adaptive_enable)");
-    const hipStream_t st = (hipStream_t)stream;
-    if (int rc = wait_finalize(c, st)) return rc;
-    const size_t npix = (size_t)c->args.tile.npix;
-    if (demodulate && !c->ad_g_valid) {
-        if (int rc = pt_gbuffer(c, c->ad_g, c->ad_g + 4 * npix, c->ad_g + 8 * npix, nullptr, st)) return rc;
-        c->ad_g_valid = true;
-    }
-    if (int rc = pt_adaptive_obj_update(c->ad, c->args.image, (float)c->args.tile.spp, demodulate ? c->ad_g + 8 * npix : nullptr, st))
-        return rc;
-    return mark_ctx(c, st);
-}
-
-int pt_adaptive_select(pt_ctx* c, const pt_adaptive_params* p, int32_t* active_blocks, int32_t* blocks) {
-    if (!c) return pt::fail(PT_ERR_ARG, "null context");
-    if (!c->ad) return pt::fail(PT_ERR_ARG, "adaptive sampling is off (pt_adaptive_enable)");
-    if (int rc = pt::adaptive_params_check(p)) return rc;
-    if (int rc = adaptive_quiesce(c)) return rc;
-    int32_t n = 0;
-    if (int rc = pt_adaptive_obj_select(c->ad, p, c->io_stream, &n, blocks)) return rc;
-    if (active_blocks) *active_blocks = n;
-    return adaptive_apply(c);
-}
-
-int pt_adaptive_set_mask(pt_ctx* c, const uint8_t* host_mask, int32_t nblocks) {
-    if (!c || !host_mask) return pt::fail(PT_ERR_ARG, "null argument");
-    if (!c->ad) return pt::fail(PT_ERR_ARG, "adaptive sampling is off (pt_adaptive_enable)");
-    if ((size_t)nblocks != c->h_cmask.size() || nblocks < 0)
-        return pt::fail(PT_ERR_ARG, "the mask length differs from the number of blocks");
-    if (int rc = adaptive_quiesce(c)) return rc;
-    if (int rc = pt_adaptive_obj_set_mask(c->ad, host_mask, nblocks, c->io_stream)) return rc;
-    return adaptive_apply(c);
-}
-
-int pt_adaptive_info(const pt_ctx* c, int32_t* on, int32_t* blocks, int32_t* active_blocks, int32_t* updates,
-                     float* batch_samples) {
-    if (!c) return pt::fail(PT_ERR_ARG, "null context");
-    if (on) *on = c->ad ? 1 : 0;
-    if (blocks) *blocks = 0;
-    if (active_blocks) *active_blocks = c->ad ? c->ad_active : 0;
-    if (updates) *updates = 0;
-    if (batch_samples) *batch_samples = 0.0f;
-    return c->ad ? pt_adaptive_obj_info(c->ad, blocks, updates, batch_samples) : PT_OK;
-}
-
-int pt_adaptive_get(pt_ctx* c, float* h_m1, float* h_m2, float* h_prev_rgb, uint32_t* h_nb, uint32_t* h_act,
-                    uint8_t* h_hot) {
-    if (!c) return pt::fail(PT_ERR_ARG, "null context");
-    if (!c->ad) return pt::fail(PT_ERR_ARG, "adaptive sampling is off (pt_adaptive_enable)");
-    if (int rc = wait_ctx(c)) return rc;
-    return pt_adaptive_obj_get(c->ad, h_m1, h_m2, h_prev_rgb, h_nb, h_act, h_hot);
-}
-
-// Resolve, the optional variance-guided filter over fresh first-hit planes (samples = 1) and the
-// copies, all on the io stream.
-int pt_adaptive_image(pt_ctx* c, const pt_denoise_var_params* prm, float* host_rgb, float* host_var) {
-    if (!c || (!host_rgb && !host_var)) return pt::fail(PT_ERR_ARG, "null argument");
-    if (!c->ad) return pt::fail(PT_ERR_ARG, "adaptive sampling is off (pt_adaptive_enable)");
-    if (prm)
-        if (int rc = pt::denoise_var_check(prm, 1.0f)) return rc;
-    int32_t updates = 0;
-    (void)pt_adaptive_obj_info(c->ad, nullptr, &updates, nullptr);
-    if (updates < 1) return pt::fail(PT_ERR_ARG, "pt_adaptive_image needs an update (pt_adaptive_update)");
-    const int W = c->args.tile.W;
-    const size_t npix = (size_t)c->args.tile.npix;
-    float* d = nullptr;   // rgb | var | filtered rgb | filtered var
-    if (hipMalloc((void**)&d, npix * 8 * sizeof(float)) != hipSuccess) return pt::fail(PT_ERR_NOMEM, "hipMalloc (adaptive image)");
-    float *d_rgb = d, *d_var = d + 3 * npix, *d_frgb = d + 4 * npix, *d_fvar = d + 7 * npix;
-    pt_denoiser* dn = nullptr;
-    int rc = wait_finalize(c, c->io_stream);
-    if (!rc) rc = pt_adaptive_obj_resolve(c->ad, c->args.image, d_rgb, d_var, c->io_stream);
-    if (!rc && prm) {
-        rc = pt_denoiser_create(W, (int32_t)(npix / W), &dn);
-        if (!rc) rc = pt_gbuffer(c, c->ad_g, c->ad_g + 4 * npix, c->ad_g + 8 * npix, nullptr, c->io_stream);
-        if (!rc) c->ad_g_valid = true;
-        if (!rc) rc = pt_denoiser_run_var(dn, d_rgb, 1.0f, d_var, c->ad_g, c->ad_g + 4 * npix, c->ad_g + 8 * npix, prm, d_frgb,
-                                          d_fvar, c->io_stream);
-    }
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        rc = mark_ctx(c, c->io_stream);
-        if (host_rgb) e = hipMemcpyAsync(host_rgb, prm ? d_frgb : d_rgb, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
-        if (e == hipSuccess && host_var)
-            e = hipMemcpyAsync(host_var, prm ? d_fvar : d_var, npix * sizeof(float), hipMemcpyDeviceToHost, c->io_stream);
-    }
-    const hipError_t e2 = hipStreamSynchronize(c->io_stream);
-    if (e == hipSuccess) e = e2;
-    pt_denoiser_destroy(dn);
-    (void)hipFree(d);
-    if (rc) return rc;
-    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_adaptive_image: ") + hipGetErrorString(e));
-    return PT_OK;
-}
-
-// ---- temporal reprojection ----------------------------------------------------
-// One frame of a pt_temporal from this context: the accumulator in place, and for a frame that is not
-// of the stored view a fresh first-hit G-buffer written straight into the object's planes.
-int pt_temporal_frame_ctx(pt_temporal* t, pt_ctx* c, float samples, void* stream) {
-    if (!t || !c) return pt::fail(PT_ERR_ARG, "null argument");
-    if (c->args.tile.world > 1) return pt::fail(PT_ERR_ARG, "pt_temporal_frame_ctx needs the whole image (world == 1)");
-    int32_t tw = 0, th = 0;
-    if (int rc = pt::temporal_size(t, &tw, &th)) return rc;
-    const int W = c->args.tile.W;
-    if (tw != W || (int64_t)tw * th != (int64_t)c->args.tile.npix)
-        return pt::fail(PT_ERR_ARG, "the temporal history and the context differ in size");
-    const int kind = pt::temporal_case(t, &c->scene_cam, samples);
-    if (kind < 0) return -kind;
-    const hipStream_t st = (hipStream_t)stream;
-    float *gA = nullptr, *gB = nullptr, *alb = nullptr;
-    if (int rc = pt::temporal_staging(t, kind, &gA, &gB, &alb)) return rc;
-    if (kind != PT_TEMPORAL_SAME_VIEW) {
-        if (int rc = pt_gbuffer(c, gA, gB, alb, nullptr, st)) return rc;   // (waits for the finalize, marks the context)
-    } else if (int rc = wait_finalize(c, st)) {
-        return rc;
-    }
-    if (int rc = pt_temporal_frame(t, &c->scene_cam, c->args.image, samples, gA, gB, alb, st)) return rc;
     return mark_ctx(c, st);
 }
 
@@ -5148,3 +4612,39 @@ int profile_read(pt_ctx* c, int32_t nkinds, double* ms, double* busy_ms, uint64_
 }
 
 }  // namespace
+
+// ---- the render side as pt_ctx_image.cpp sees it (pt_ctx.h) -------------------------------------
+pt::CtxHead* pt::ctx_head(pt_ctx* c) { return c; }
+
+int pt::adaptive_quiesce(pt_ctx* c) {
+    if (int rc = wait_ctx(c)) return rc;
+    if (c->ahead_recorded) {
+        HIP_TRY(hipEventSynchronize(c->ev_ahead));
+        if (c->ahead_valid) {
+            if (int rc = settle_ahead(c, c->io_stream, false)) return rc;
+            HIP_TRY(hipStreamSynchronize(c->io_stream));
+        }
+    }
+    return PT_OK;
+}
+
+const char* pt::adaptive_refusal(const pt_ctx* c) {
+    if (!c->args.cmask)
+        return "adaptive sampling needs first-bounce camera masks (an analytic scene of at most 32 geoms without triangles, "
+               "PT_AMD_NO_CMASK unset)";
+    if (!c->fused && !c->flags.sort_by_material)
+        return "adaptive sampling needs the fused or the material-sorted pipeline (PT_PIPELINE=split joins the masks of "
+               "neighbouring blocks)";
+    if (c->args.fl.verify) return "adaptive sampling with PT_AMD_VERIFY_BOUNDS=1 (the verifying kernels ignore the masks)";
+    return nullptr;
+}
+
+pt::CameraMasks pt::camera_masks(const pt_ctx* c) { return {c->d_cmask, c->h_cmask.size()}; }
+
+void pt::point_cmask(pt_ctx* c, const uint32_t* masks, const uint32_t* act) {
+    const size_t nblk = c->h_cmask.size();
+    size_t empty = 0;
+    for (size_t b = 0; b < nblk; ++b) empty += (act && act[b] == 0u) || c->h_cmask[b] == 0u;
+    choose_cmask_skip(c, empty, nblk);
+    c->args.cmask = masks ? masks : c->d_cmask;
+}

@@ -1,5 +1,7 @@
 # A variant library built from another version of pt_kernels.hip (e.g. git HEAD) for A/B runs:
 #   scripts/build_file_variant.sh NAME FILE [extra hipcc flags]  -> cuda_pathtracer_amd/build/libpt_amd_NAME.so
+# FILE links with this tree's other objects, pt_ctx_image.cpp's among them: a pt_kernels.hip from before the image-level
+# entry points moved there (pt_get_image, pt_denoise_image, pt_adaptive_*, ...) defines them a second time and does not link.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 B=$R/cuda_pathtracer_amd/build

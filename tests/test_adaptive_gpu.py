@@ -490,6 +490,70 @@ def test_adaptive_image_equals_resolve_and_the_host_filter(gpu_device):
     ctx.free()
 
 
+def test_variance_tracking_and_adaptive_sampling_in_turn_on_one_context(gpu_device):
+    """The two features exclude each other and share the context's first-hit planes and their valid flag.
+    One context that tracks variance, then samples adaptively, then tracks variance again reads, at every
+    step, the bits that fresh contexts read which only ever use one of the two: a plane buffer freed or
+    allocated with its flag left set would demodulate by stale or unwritten albedo.  (The last phase runs
+    a second pass so that its moments can be read too: a variance needs two batches.)"""
+    w, h, spp = 72, 40, 4
+    scene = _scene(w, h)
+    prm = N.DenoiseVarParams.default()
+
+    def passes(ctx, iters, update):
+        for it in iters:
+            ctx.render_pass(it)
+            update()
+
+    def adaptive_reads(ctx):
+        passes(ctx, (1, 5), ctx.adaptive_update)
+        state = ctx.adaptive_state()
+        return state, ctx.adaptive_image(return_variance=True), ctx.adaptive_image(prm, return_variance=True)
+
+    def tail_reads(ctx):
+        ctx.track_variance(True)
+        passes(ctx, (9,), ctx.variance_update)
+        acc = ctx.image()
+        passes(ctx, (13,), ctx.variance_update)
+        return acc, ctx.variance(float(2 * spp)), ctx.image()
+
+    mix = P.PathTracer(scene, _gui(), spp=spp)
+    mix.track_variance(True)
+    passes(mix, (1, 5), mix.variance_update)
+    mix_var = mix.variance(float(2 * spp))
+    mix.track_variance(False)
+    mix.reset_image()
+    mix.adaptive(True)
+    mix_ad = adaptive_reads(mix)
+    mix.adaptive(False)
+    mix_tail = tail_reads(mix)
+    mix.free()
+
+    var_only = P.PathTracer(scene, _gui(), spp=spp)
+    var_only.track_variance(True)
+    passes(var_only, (1, 5), var_only.variance_update)
+    _same(mix_var, var_only.variance(float(2 * spp)), "variance before adaptive sampling")
+    var_only.free()
+
+    ad_only = P.PathTracer(scene, _gui(), spp=spp)
+    ad_only.adaptive(True)
+    state, resolved, filtered = adaptive_reads(ad_only)
+    ad_only.free()
+    for k in ("m1", "m2", "prev", "nb", "act", "hot"):
+        _same(mix_ad[0][k], state[k], ("adaptive state", k))
+    for got, want, what in zip(mix_ad[1] + mix_ad[2], resolved + filtered,
+                               ("resolved image", "resolved variance", "filtered image", "filtered variance")):
+        _same(got, want, what)
+
+    tail = P.PathTracer(scene, _gui(), spp=spp)
+    passes(tail, (1, 5), lambda: None)
+    want_tail = tail_reads(tail)
+    tail.free()
+    for got, want, what in zip(mix_tail, want_tail, ("accumulator after one more pass", "variance after adaptive sampling",
+                                                     "final accumulator")):
+        _same(got, want, what)
+
+
 # ---- end to end ---------------------------------------------------------------------------------------------
 def test_first_selection_on_the_scene_the_oracle_chose(gpu_device):
     """E2E (tests/test_adaptive_cpu.py) was chosen so that the first selection turns some blocks off and
