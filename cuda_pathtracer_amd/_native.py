@@ -190,6 +190,7 @@ SIGNATURES = {
     "pt_ctx_cmask_info": (_I, [_P, _IP, C.POINTER(C.c_double), _IP]),
     "pt_ctx_room_info": (_I, [_P, _IP, _IP, _FP, _FP]),
     "pt_ctx_depart_counts": (_I, [_P] + [C.POINTER(C.c_uint64)] * 3),
+    "pt_ctx_exact_counts": (_I, [_P] + [C.POINTER(C.c_uint64)] * 2),
     "pt_ctx_counters": (_I, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pt_ctx_stream_info": (_I, [_P] + [C.POINTER(C.c_int32)] * 5),
     "pt_ctx_walk_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_double)]),
@@ -209,6 +210,7 @@ SIGNATURES = {
     "pt_stats": (_I, [_P, C.POINTER(Stats)]),
     "pt_profile_enable": (_I, [_P, _I]),
     "pt_selftest_math": (_I, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "pt_selftest_exact": (_I, [C.c_uint64, C.c_uint32] + [C.POINTER(C.c_uint64)] * 3),
     "pt_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "pt_profile_read_busy": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "pt_profile_read_kinds": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
@@ -289,8 +291,10 @@ def _preload_torch() -> None:
 # library has them all; pt_ctx_room_info: the A/B against the build before the room bound;
 # pt_scene_room_info: the A/B against the build before the host-only bounds unit; the
 # variance entry points, pt_temporal_* and pt_adaptive_*: the A/B against the builds before them;
-# pt_ctx_depart_counts: the A/B against the build before the room's departure claim).
+# pt_ctx_depart_counts: the A/B against the build before the room's departure claim;
+# pt_ctx_exact_counts, pt_selftest_exact: the A/B against the build before the exact tests' single gate).
 _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
+             "pt_ctx_exact_counts", "pt_selftest_exact",
              "pt_moments_create",
              "pt_moments_destroy", "pt_moments_reset", "pt_moments_update", "pt_moments_info", "pt_moments_variance",
              "pt_moments_get", "pt_denoise_var_params_default", "pt_denoiser_run_var", "pt_denoise_var_host",

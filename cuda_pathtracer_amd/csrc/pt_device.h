@@ -93,6 +93,48 @@ __device__ __forceinline__ f3 normalize(f3 v) {
     return v * inv;
 }
 __device__ __forceinline__ float length(f3 v) { return sqrt_cr(dot(v, v)); }
+// normalize's core for x = dot(v, v): what normalize returns when x passes its range test
+__device__ __forceinline__ f3 norm_core(f3 v, float x) {
+    const float s = sqrt_core(x);
+    return v * div_core(1.0f, s, recip_core(s));
+}
+
+// ---- one range gate for a whole exact test (pt_kernels.hip exact_geom) --------
+// The per-operation forms above pay a compare, an exec-mask region and a branch for each sqrt,
+// division and normalize.  A fast path runs the cores unconditionally and feeds every gated operand
+// to one RangeGate instead: two running unsigned words (v_add / v_sub, v_min3 / v_max3: no SGPR,
+// no exec change), compared once at the end of the test.  ok() holds exactly
+// when every operand fed passed the range its per-operation form states above:
+//   div_lo / div_hi (the smallest and the largest magnitude of a group of division operands):
+//            |v| in [2^-40, 2^40]   <=> bits(|v|) in [kLo, kHi]  (a float's order is its bit pattern's
+//            for non-negative values; zero and denormals lie below kLo, inf above kHi);
+//   norm(x): x in [2^-80, 2^80]     <=> u = bits(x) in [kLo - D, kHi + D] with D = 40 << 23.  mn takes
+//            u + D, mx takes u - D.  u + D wraps only for u >= 2^32 - D (sign bit set: out of range) and
+//            is then < D < kLo: tripped; u - D wraps only for u < D (x < 2^-87: out of range) and is then
+//            > kHi: tripped; without a wrap the two comparisons are u >= kLo - D and u <= kHi + D;
+//   root(x): x in [2^-96, FLT_MAX]  <=> u in [31 << 23, 0x7f7fffff].  mn takes u + (56 << 23) (>= kLo iff
+//            u >= 31 << 23; a wrap needs the sign bit and gives < kLo: tripped), mx takes the saturating
+//            u - (0x7f7fffff - kHi) (<= kHi iff u <= 0x7f7fffff: -0, negative values, inf and NaN trip).
+struct RangeGate {
+    static constexpr uint32_t kLo = 0x2b800000u, kHi = 0x53800000u;   // bits of 2^-40 and 2^40
+    uint32_t mn = kHi, mx = kLo;
+    // Several division operands at once: lo = the smallest, hi = the largest of their magnitudes, taken
+    // with fminf / fmaxf of fabsf (v_min3_f32 / v_max3_f32 with |x| source modifiers: no v_and).  Those
+    // skip a NaN operand, so the caller shows that none of the operands is one, or trips the gate itself.
+    __device__ __forceinline__ void div_lo(float lo) { mn = min(mn, __float_as_uint(lo)); }
+    __device__ __forceinline__ void div_hi(float hi) { mx = max(mx, __float_as_uint(hi)); }
+    __device__ __forceinline__ void norm(float x) {
+        const uint32_t u = __float_as_uint(x);
+        mn = min(mn, u + (40u << 23));
+        mx = max(mx, u - (40u << 23));
+    }
+    __device__ __forceinline__ void root(float x) {
+        const uint32_t u = __float_as_uint(x);
+        mn = min(mn, u + (56u << 23));
+        mx = max(mx, __builtin_elementwise_sub_sat(u, 0x7f7fffffu - kHi));
+    }
+    __device__ __forceinline__ bool ok() const { return mn >= kLo && mx <= kHi; }
+};
 __device__ __forceinline__ float gmin(float a, float b) { return a < b ? a : b; }
 __device__ __forceinline__ float gmax(float a, float b) { return a > b ? a : b; }
 __device__ __forceinline__ float at(f3 v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }

@@ -72,6 +72,9 @@ struct DevStats {
     uint32_t loop_zero;     // (ray, loop cube) pairs left as candidates with bound 0 (bound_wbox_tagged)
     uint32_t loop_depart;   // of those, the origin beyond the cube's own widened slab and moving away
     uint32_t pad_;
+    // likewise (pt_ctx_exact_counts): exact tests of the bounded closest hit (exact_geom), and those
+    // of them whose range gate tripped, so the literal path ran
+    unsigned long long exact_tests, exact_tripped;
 };
 
 struct SceneDev {
@@ -854,7 +857,9 @@ __device__ __forceinline__ uint32_t bound_obox_tagged(const G& g, f3 ro, f3 rd, 
 // sphereIntersectionTest (:60-115) with their common prologue (object-space ray) and epilogue
 // (pointOnRay, back-transform, world length) shared, so a wave whose lanes test different geom
 // types runs only the type-specific middle twice.  Same operations, same order: bit-identical.
-__device__ __forceinline__ float exact_geom(const LGeom& L, f3 r_o, f3 r_d, int& code, f3& obj, bool& outside) {
+// This is the LITERAL path: every sqrt, division and normalize behind its own range test (pt_device.h).
+__device__ __forceinline__ float exact_geom_literal(const LGeom& L, f3 r_o, f3 r_d, int& code, f3& obj,
+                                                    bool& outside) {
     code = -1;
     outside = true;
     const int type = L.type;
@@ -895,6 +900,117 @@ __device__ __forceinline__ float exact_geom(const LGeom& L, f3 r_o, f3 r_d, int&
     return length(r_o - ip);
 }
 
+// The exact test the bounded closest hit runs: a straight-line FAST path under one range gate, and
+// exact_geom_literal for the lanes whose gate tripped (they recompute the whole test; a cold block).
+// The fast path runs the cores of every sqrt, division and normalize of the literal path
+// unconditionally, in the literal path's order, and feeds the operands the literal path range-tests
+// to one RangeGate (pt_device.h): the radicand qq of the first normalize and that of length(), the
+// sphere's radicand, and the two numerators and the divisor of each slab axis.  Where the gate passes,
+// every per-operation test of the literal path passes and its cores are the ones run here: the same bits.
+// What the gate excludes, and why each form the fast path writes differently is bit-identical on the rest:
+//  - The direction.  With qq = dot(qv, qv) in [2^-80, 2^80] every component of qv is finite (a NaN or
+//    infinite one makes qq NaN or infinite), s = sqrt(qq) lies in [2^-40, 2^40] and 1 / s is finite and
+//    normal, so no component of qd = qv * (1 / s) is a NaN.  Each is qv_k / |qv| within a few 2^-23
+//    relative (products below 2^-126 that underflow in qq are below 2^-46 of it), so |qd_k| <= 1 + 2^-20
+//    and dot(qd, qd) is within 2^-20 of 1: the radicand of point_on_ray's normalize always passes
+//    its range test and is not fed to the gate.
+//  - Cube.  With |n|, |d| in [2^-40, 2^40] every slab parameter t1, t2 is a correctly rounded quotient
+//    with magnitude in [2^-80, 2^80]: finite, not NaN, not zero.  On such values
+//      a < b ? a : b == fminf(a, b) and a > b ? a : b == fmaxf(a, b)  (no NaN to order, no +-0 pair to
+//      tell apart; equal values have equal bits);
+//      the literal loop's tmin is -1e38 until the first ta > 0 and then the largest positive ta, its nmin
+//      the first axis that reached it (strict >): tm = max(ta0, ta1, ta2, 0) is that maximum or 0 for
+//      "none", and `tm == ta_k` in axis order names the same axis (an axis with ta <= 0 cannot equal
+//      tm > 0; nmin is read only when tm > 0);
+//      tb <= 2^80 < 1e38, so the literal tmax is min(tb0, tb1, tb2) and nmax the first axis equal to it
+//      (strict <);
+//      `tmax >= tmin && tmax > 0` with tmin = -1e38 is `tmax > 0`, and so is `tmax >= 0 && tmax > 0`;
+//      `tmin <= 0` is `!(tm > 0)`.
+//    A zero, denormal, infinite or NaN direction component or numerator (an axis-parallel ray, an
+//    origin on a slab plane, a NaN direction or origin) trips the gate.
+//  - Sphere.  A negative radicand is a miss whatever its root (`hit` is false and t is not read), so
+//    it feeds the gate a 1 instead of tripping it; every other radicand (NaN included) is fed as it
+//    is.  The selection of t keeps the literal compare-select forms.
+//  - The epilogue runs, and feeds the gate, only for lanes that hit, as in the literal path.
+// code, obj and outside are meaningful only for a hit (t > 0), the only case in which the callers
+// read them.  COUNT (the CHECK / VERIFY instantiations): DevStats::exact_tests / exact_tripped.
+template <bool COUNT = false>
+__device__ __forceinline__ float exact_geom(const LGeom& L, f3 r_o, f3 r_d, int& code, f3& obj, bool& outside,
+                                            DevStats* cnt = nullptr, bool* tripped = nullptr) {
+    code = -1;
+    outside = true;
+    const int type = L.type;
+    if (type != PT_GEOM_CUBE && type != PT_GEOM_SPHERE) return -1.0f;
+    RangeGate gate;
+    const f3 qo = xform_point(L.inv, r_o);
+    const f3 qv = xform_vector(L.inv, r_d);
+    const float qq = dot(qv, qv);
+    gate.norm(qq);
+    const f3 qd = norm_core(qv, qq);
+    float t;
+    bool hit, onan = false;
+    if (type == PT_GEOM_CUBE) {
+        float ta[3], tb[3], n1[3], n2[3];
+        int c[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            n1[a] = -0.5f - at(qo, a);
+            n2[a] = +0.5f - at(qo, a);
+        }
+        // the nine division operands (RangeGate::div_lo / div_hi).  The divisors: no component of qd is a
+        // NaN or exceeds 1 + 2^-20 once qq has passed (see above), so only their smallest magnitude is fed.
+        // The numerators: a NaN one needs a NaN origin component, tested on its own below.
+        gate.div_lo(fminf(fminf(fabsf(qd.x), fabsf(qd.y)), fabsf(qd.z)));
+        gate.div_lo(fminf(fminf(fabsf(n1[0]), fabsf(n2[0])), fabsf(n1[1])));
+        gate.div_lo(fminf(fminf(fabsf(n2[1]), fabsf(n1[2])), fabsf(n2[2])));
+        gate.div_hi(fmaxf(fmaxf(fabsf(n1[0]), fabsf(n2[0])), fabsf(n1[1])));
+        gate.div_hi(fmaxf(fmaxf(fabsf(n2[1]), fabsf(n1[2])), fabsf(n2[2])));
+        onan = __builtin_isunordered(qo.x, qo.y) | (qo.z != qo.z);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float qa = at(qd, a);
+            const float r = recip_core(qa);
+            const float t1 = div_core(n1[a], qa, r), t2 = div_core(n2[a], qa, r);
+            ta[a] = fminf(t1, t2);
+            tb[a] = fmaxf(t1, t2);
+            c[a] = 2 * a + (t2 < t1 ? 0 : 1);
+        }
+        const float tm = fmaxf(fmaxf(fmaxf(ta[0], ta[1]), ta[2]), 0.0f);
+        const float tx = fminf(fminf(tb[0], tb[1]), tb[2]);
+        const int nmin = tm == ta[0] ? c[0] : (tm == ta[1] ? c[1] : c[2]);
+        const int nmax = tx == tb[0] ? c[0] : (tx == tb[1] ? c[1] : c[2]);
+        hit = tx >= tm && tx > 0;
+        const bool entered = tm > 0;
+        t = entered ? tm : tx;
+        code = entered ? nmin : nmax;
+    } else {
+        const float vdd = dot(qo, qd);
+        const float radicand = vdd * vdd - (dot(qo, qo) - 0.25f);
+        gate.root(radicand < 0 ? 1.0f : radicand);
+        const float sq = sqrt_core(radicand);
+        const float t1 = -vdd + sq, t2 = -vdd - sq;
+        hit = !(radicand < 0) && !(t1 < 0 && t2 < 0);
+        if (t1 > 0 && t2 > 0) { t = gmin(t1, t2); outside = true; }
+        else { t = gmax(t1, t2); outside = false; }
+    }
+    float res = -1.0f;
+    if (hit) {
+        obj = qo + (t - .0001f) * norm_core(qd, dot(qd, qd));   // point_on_ray: its radicand needs no test (above)
+        const f3 w = r_o - xform_point(L.xf, obj);
+        const float ww = dot(w, w);
+        gate.root(ww);
+        res = sqrt_core(ww);   // length
+    }
+    const bool ok = gate.ok() & !onan;
+    if (COUNT && cnt) {
+        atomicAdd(&cnt->exact_tests, 1ull);
+        if (!ok) atomicAdd(&cnt->exact_tripped, 1ull);
+    }
+    if (tripped) *tripped = !ok;
+    if (__builtin_expect(!ok, 0)) res = exact_geom_literal(L, r_o, r_d, code, obj, outside);
+    return res;
+}
+
 // PRE: scenes with meshes whose BVH closest hit `mh` came from k_traverse.  The owning mesh geom
 // (the first in index order whose triangle range holds the hit, intersect_scene's rule) enters as an
 // exactly evaluated hit before the exact tests; mesh geoms have no bound (bkind 0).
@@ -905,7 +1021,7 @@ __device__ __forceinline__ uint32_t ng_all_mask(int n) { return n >= 32 ? ~0u : 
 #if defined(PT_DUP)
 __device__ uint32_t g_dup_sink;
 #endif
-// COUNT, cnt: the departure counters of the CHECK / VERIFY instantiations (DevStats::room_depart, loop_*).
+// COUNT, cnt: the counters of the CHECK / VERIFY instantiations (DevStats::room_depart, loop_*, exact_*).
 template <bool SEL, bool PRE = false, bool COUNT = false>
 __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsDev& fl, const LGeom* s_geoms, f3 ro,
                                                  f3 rd, const MeshHit* mh = nullptr, uint32_t gmask = ~0u,
@@ -1065,7 +1181,8 @@ __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsD
         rest = ng_all_mask(S.ngeoms);   // a direction the bounds do not cover: the reference's loop over every geom
     }
     if (PRE && plain) return intersect_scene<PRE, PRE>(S, fl, ro, rd, mh);
-    {   // pass 2, one loop over the candidates (so the kernels carry one inlined exact test): the first;
+    {   // pass 2, one loop over the candidates (one call of the exact test in the source; the compiler keeps
+        // two inlined copies, the first candidate's and the loop's): the first;
         // the second while its bound does not exceed the best hit; then, if the third-smallest bound does
         // not, every other geom the wave may hit (one with no finite bound misses exactly, so testing it
         // changes nothing; rare: 0 rays on Cornell and config 4).  The selection is order-independent
@@ -1074,7 +1191,7 @@ __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsD
             int code;
             f3 obj = F3(0, 0, 0);
             bool outside;
-            const float t = exact_geom(s_geoms[gi], ro, rd, code, obj, outside);
+            const float t = exact_geom<COUNT>(s_geoms[gi], ro, rd, code, obj, outside, cnt);
 #if defined(PT_DUP) && PT_DUP == 8   // diagnostic: every exact test again (its cost x the tests per ray)
             if (SEL) {
                 f3 r2 = ro;
@@ -1086,7 +1203,8 @@ __device__ __forceinline__ Hit intersect_bounded(const SceneDev& S, const FlagsD
                 if (__float_as_uint(t2) == 0x7f7ffffeu) atomicAdd(&g_dup_sink, 1u);
             }
 #endif
-            if (t > 0.0f && (t_min > t || (t == t_min && hit_geom >= 0 && gi < hit_geom))) {
+            // (one mask from plain comparisons: && and || compiled to three nested exec regions)
+            if ((t > 0.0f) & ((t_min > t) | ((t == t_min) & (hit_geom >= 0) & (gi < hit_geom)))) {
                 t_min = t; hit_geom = gi; best_code = code; best_obj = obj; best_outside = outside;
             }
         };
@@ -1451,8 +1569,10 @@ __device__ __forceinline__ const KArgs& fresh_args() { return fresh_param<KArgs>
 // inter-workgroup dependency (any grid size is correct).  Survivors are written back IN PLACE
 // and flagged; the stable compaction runs in k_compact_paths.  The RNG key of a path is its
 // index i in the compacted input (pathtrace.cu:315).
+// (the analytic instantiations took 8 waves per SIMD unasked before the exact test's fast path kept its three
+// slab axes live at once; 8 asked for now spills 4 VGPRs next to the verifying loop, 7 caps them at 72)
 template <bool FIRST, bool SPP1, bool MESH>
-__global__ __launch_bounds__(kBlock) void k_trace(const KArgs A) {
+__global__ __launch_bounds__(kBlock, MESH ? 1 : 7) void k_trace(const KArgs A) {
     __shared__ DMaterial s_mats[kLdsMats];
     __shared__ LGeom s_geoms[MESH ? 1 : kLdsGeoms];
     __shared__ uint32_t s_cnt;
@@ -2326,7 +2446,8 @@ constexpr int kLaterWaves = 8; // (minimum waves per SIMD of the later-bounce ke
 constexpr int kFirstWaves = 8;   // (minimum waves per SIMD of the analytic first-bounce kernels: 8 caps them at 64
                                  // VGPRs, one spilled; Cornell +1.8%, first bounce -11% per launch, profiles/r06_first_waves_ab.txt)
 template <bool FIRST, bool SPP1, int MESH>
-__global__ __launch_bounds__(kBlock, (MESH != 0 && MESH != kAnalyticSkip) ? 1 : (FIRST ? kFirstWaves : kLaterWaves))
+// (kAnalyticGM took 8 waves unasked until the exact test's fast path kept its three slab axes live at once)
+__global__ __launch_bounds__(kBlock, (MESH == kMeshInline || MESH == kMeshPre) ? 1 : (FIRST ? kFirstWaves : kLaterWaves))
 void k_bounce(const KArgs A) {
     // scene tables sized to the scene (dynamic LDS, bounce_lds_bytes): geom rows, then materials
     extern __shared__ __align__(16) uint8_t s_dyn[];
@@ -3244,6 +3365,9 @@ __global__ void k_ahead_settle(float* __restrict__ image, const v4f* __restrict_
         ast->err = 0u;
         ast->bound_mismatch = 0u;
         ast->room_depart = ast->loop_zero = ast->loop_depart = 0u;
+        st->exact_tests += ast->exact_tests;
+        st->exact_tripped += ast->exact_tripped;
+        ast->exact_tests = ast->exact_tripped = 0ull;
     }
 }
 
@@ -3291,6 +3415,66 @@ __global__ void k_selftest_math(uint64_t n, uint32_t seed, unsigned long long* b
         e += same_bits(length(v), sqrtf(dot(v, v))) ? 0 : 1;
     }
     if (e) atomicAdd(bad, e);
+}
+
+// pt_selftest_exact: exact_geom (fast path under one gate, literal fallback) against exact_geom_literal.
+// Pair i, by i & 3: 0 and 1 — ordinary operands (ray origin in [-3, 3)^3, direction in [-1, 1)^3, map
+// entries in [-1.5, 1.5), translations in [-2, 2)); 2 — the same with one ray component replaced by
+// selftest_operand's slot 0 (a random bit pattern or an edge operand), the linear parts diagonal for
+// half of them so that a zero direction component reaches a slab as a zero divisor; 3 — every ray
+// component and map entry from selftest_operand.  out[0] mismatches, out[1] tripped gates, out[2]
+// pairs the fast path answered.
+__global__ void k_selftest_exact(uint64_t n, uint32_t seed, unsigned long long* out) {
+    unsigned long long bad = 0, trip = 0, fast = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t h = utilhash((uint32_t)i ^ seed ^ (uint32_t)(i >> 32) * 0x9e3779b9u);
+        const int cls = (int)(i & 3);
+        auto next = [&]() { h = utilhash(h + 0x7f4a7c15u); return h; };
+        auto uni = [&](float half) { return ((float)(next() >> 8) * 0x1p-23f - 1.0f) * half; };   // [-half, half)
+        int slot = 0;
+        auto val = [&](float half) { return cls == 3 ? selftest_operand(next(), i, slot++ % 3) : uni(half); };
+        LGeom L;
+        L.type = (next() & 1u) ? PT_GEOM_CUBE : PT_GEOM_SPHERE;
+        L.material = 0;
+        const bool diag = cls == 2 && (next() & 1u);
+        Affine* maps[2] = {&L.inv, &L.xf};
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+#pragma unroll
+            for (int col = 0; col < 4; ++col)
+#pragma unroll
+                for (int row = 0; row < 3; ++row) {
+                    const float v = val(col == 3 ? 2.0f : 1.5f);
+                    maps[m]->c[col][row] = (diag && col < 3 && col != row) ? 0.0f : v;
+                }
+            maps[m]->z3[0] = maps[m]->z3[1] = maps[m]->z3[2] = 0.0f;
+        }
+        float r[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) r[k] = val(k < 3 ? 3.0f : 1.0f);
+        if (cls == 2) {
+            const uint32_t which = next() % 6u;
+            const float e = selftest_operand(next(), i, 0);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) r[k] = (uint32_t)k == which ? e : r[k];
+        }
+        const f3 ro = F3(r[0], r[1], r[2]), rd = F3(r[3], r[4], r[5]);
+        int code, codel;
+        f3 obj = F3(0, 0, 0), objl = F3(0, 0, 0);
+        bool outside, outsidel, tripped = false;
+        const float t = exact_geom(L, ro, rd, code, obj, outside, nullptr, &tripped);
+        const float tl = exact_geom_literal(L, ro, rd, codel, objl, outsidel);
+        bool same = same_bits(t, tl);
+        if (tl > 0.0f)
+            same = same && code == codel && outside == outsidel && same_bits(obj.x, objl.x) &&
+                   same_bits(obj.y, objl.y) && same_bits(obj.z, objl.z);
+        bad += same ? 0 : 1;
+        trip += tripped ? 1 : 0;
+        fast += tripped ? 0 : 1;
+    }
+    if (bad) atomicAdd(out + 0, bad);
+    if (trip) atomicAdd(out + 1, trip);
+    if (fast) atomicAdd(out + 2, fast);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4147,6 +4331,16 @@ int pt_ctx_depart_counts(pt_ctx* c, uint64_t* room, uint64_t* loop_zero, uint64_
     return PT_OK;
 }
 
+int pt_ctx_exact_counts(pt_ctx* c, uint64_t* tests, uint64_t* tripped) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    if (int rc = wait_ctx(c)) return rc;
+    DevStats s;
+    HIP_TRY(io_copy(c, &s, c->stats, sizeof s, hipMemcpyDeviceToHost));
+    if (tests) *tests = s.exact_tests;
+    if (tripped) *tripped = s.exact_tripped;
+    return PT_OK;
+}
+
 int pt_ctx_stream_info(const pt_ctx* c, int32_t* lanes, int32_t* busy_streams, int32_t* process_busy,
                        int32_t* hw_queues, int32_t* lanes_capped) {
     if (!c) return pt::fail(PT_ERR_ARG, "null context");
@@ -4546,6 +4740,25 @@ int pt_selftest_math(uint64_t n, uint32_t seed, uint64_t* mismatches) {
     (void)hipFree(d);
     if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("selftest: ") + hipGetErrorString(e));
     *mismatches = h;
+    return PT_OK;
+}
+
+int pt_selftest_exact(uint64_t n, uint32_t seed, uint64_t* mismatches, uint64_t* tripped, uint64_t* fast) {
+    if (!mismatches || !tripped || !fast) return pt::fail(PT_ERR_ARG, "null argument");
+    unsigned long long* d = nullptr;
+    unsigned long long h[3] = {0, 0, 0};
+    HIP_TRY(hipMalloc(&d, sizeof h));
+    hipError_t e = hipMemset(d, 0, sizeof h);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_selftest_exact, dim3(1024), dim3(256), 0, nullptr, n, seed, d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);   // (synchronises)
+    (void)hipFree(d);
+    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("selftest: ") + hipGetErrorString(e));
+    *mismatches = h[0];
+    *tripped = h[1];
+    *fast = h[2];
     return PT_OK;
 }
 

@@ -359,6 +359,15 @@ class PathTracer:
         check_pt(lib().pt_ctx_depart_counts(self._h, *[C.byref(x) for x in v]))
         return {"room": int(v[0].value), "loop_zero": int(v[1].value), "loop_depart": int(v[2].value)}
 
+    def exact_counts(self) -> dict:
+        """PT_AMD_VERIFY_BOUNDS=1 only (pt_ctx_exact_counts): exact tests the bounded closest hit ran,
+        and those whose range gate tripped (the literal path recomputed them)."""
+        if not hasattr(lib(), "pt_ctx_exact_counts"):
+            raise N.NativeLibraryError("the loaded library (PT_AMD_LIB) predates pt_ctx_exact_counts")
+        v = [C.c_uint64() for _ in range(2)]
+        check_pt(lib().pt_ctx_exact_counts(self._h, *[C.byref(x) for x in v]))
+        return {"tests": int(v[0].value), "tripped": int(v[1].value)}
+
     def walk_info(self) -> dict:
         """Mesh scenes: 4-wide walk on/off, its exact t-cull on/off and the share of slots whose
         cull margin can pay (pt_ctx_walk_info)."""

@@ -264,6 +264,12 @@ int pt_ctx_room_info(const pt_ctx* c, int32_t* walls, int32_t* faces, float* lo,
  * slab with the ray not coming back (what the same claim could remove there).  Waits for the context's
  * queued work.  Any pointer may be null. */
 int pt_ctx_depart_counts(pt_ctx* c, uint64_t* room, uint64_t* loop_zero, uint64_t* loop_depart);
+/* Inspection, PT_AMD_VERIFY_BOUNDS=1 only (zeros otherwise; counted like pt_ctx_depart_counts): tests —
+ * exact tests the bounded closest hit ran (one per ray and candidate geom); tripped — those of them
+ * whose range gate tripped, so the whole test ran again through the literal, per-operation-gated path
+ * (DESIGN.md §3): an operand of a sqrt, division or normalize that is zero, denormal, infinite, NaN or
+ * outside the core's range.  Waits for the context's queued work.  Either pointer may be null. */
+int pt_ctx_exact_counts(pt_ctx* c, uint64_t* tests, uint64_t* tripped);
 /* Mesh scenes: whether the BVH walk runs on the 4-wide layout, whether its exact t-cull is on, and
  * the share of the layout's slots whose cull margin can pay.  The cull is on when
  * that share is >= 1/4 (PT_AMD_TCULL=0/1 forces it); it never changes a result. */
@@ -361,6 +367,13 @@ int pt_profile_read_kinds(pt_ctx* c, int32_t nkinds, double* ms, double* busy_ms
  * patterns over every exponent, a quarter near 1, plus zeros, denormals, infinities and NaNs).
  * *mismatches = operations whose bits differ (NaN == NaN).  Synchronous. */
 int pt_selftest_math(uint64_t n, uint32_t seed, uint64_t* mismatches);
+/* Device self-check of the exact test's fast path (one range gate) against its literal
+ * path: n (ray, geom) pairs from `seed` — cubes and spheres under random affine maps, half of the pairs
+ * with ordinary operands and half with pt_selftest_math's operands (every exponent, zeros, denormals,
+ * infinities, NaNs) in the ray and the maps.  *mismatches = pairs whose distance bits differ (NaN ==
+ * NaN) or, for a hit, whose slab code, object-space point or side differ; *tripped = pairs whose gate
+ * tripped; *fast = pairs the fast path answered.  Synchronous. */
+int pt_selftest_exact(uint64_t n, uint32_t seed, uint64_t* mismatches, uint64_t* tripped, uint64_t* fast);
 
 /* ---- texture input --------------------------------------------------------------------- */
 /* Texture::load (sceneStructs.h:171-175) = stbi_load(file, &w, &h, &comp, 0) for JPEG data:
