@@ -121,6 +121,19 @@ class AdaptiveParams(C.Structure):
         return p
 
 
+class JpegParams(C.Structure):
+    """pt_jpeg_params; JpegParams.default() = pt_jpeg_params_default (quality 90, 4:2:0, no mirror)."""
+    _fields_ = [("quality", C.c_int32), ("subsampling", C.c_int32), ("mirror_x", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+    @classmethod
+    def default(cls) -> "JpegParams":
+        p = cls()
+        lib().pt_jpeg_params_default(C.byref(p))
+        return p
+
+
+JPEG_444, JPEG_420 = 0, 1   # PT_JPEG_*
+assert C.sizeof(JpegParams) == 32
 assert C.sizeof(DenoiseParams) == 32 and C.sizeof(DenoiseVarParams) == 32 and C.sizeof(TemporalParams) == 32
 assert C.sizeof(AdaptiveParams) == 32
 assert C.sizeof(Geom) == 272 and C.sizeof(Material) == 48 and C.sizeof(Triangle) == 124
@@ -272,6 +285,17 @@ SIGNATURES = {
     "pt_adaptive_info": (_I, [_P, _IP, _IP, _IP, _IP, _FP]),
     "pt_adaptive_get": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "pt_adaptive_image": (_I, [_P, C.POINTER(DenoiseVarParams), _P, _P]),
+    "pt_jpeg_params_default": (None, [C.POINTER(JpegParams)]),
+    "pt_jpeg_enc_create": (_I, [_I, _I, C.POINTER(JpegParams), C.POINTER(_P)]),
+    "pt_jpeg_enc_destroy": (_I, [_P]),
+    "pt_jpeg_enc_bound": (C.c_int64, [_P]),
+    "pt_jpeg_enc_header": (C.c_int64, [_P, _P, C.c_int64]),
+    "pt_jpeg_enc_pixels": (_I, [_P, _P, _I, _P, C.c_int64, _P, _P]),
+    "pt_jpeg_enc_accum": (_I, [_P, _P, _F, _P, C.c_int64, _P, _P]),
+    "pt_jpeg_encode_host": (_I, [_I, _I, _P, _I, C.POINTER(JpegParams), _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "pt_preview_jpeg": (_I, [_P, _I, _P, _P, C.c_int64, _P, _P]),
+    "pt_jpeg_enc_profile": (_I, [_P, _I]),
+    "pt_jpeg_enc_profile_read": (_I, [_P, _FP]),
 }
 
 _lib = None
@@ -292,7 +316,8 @@ def _preload_torch() -> None:
 # pt_scene_room_info: the A/B against the build before the host-only bounds unit; the
 # variance entry points, pt_temporal_* and pt_adaptive_*: the A/B against the builds before them;
 # pt_ctx_depart_counts: the A/B against the build before the room's departure claim;
-# pt_ctx_exact_counts, pt_selftest_exact: the A/B against the build before the exact tests' single gate).
+# pt_ctx_exact_counts, pt_selftest_exact: the A/B against the build before the exact tests' single gate;
+# pt_jpeg_*, pt_preview_jpeg: the A/B against the build before the JPEG encoder).
 _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
              "pt_ctx_exact_counts", "pt_selftest_exact",
              "pt_moments_create",
@@ -306,7 +331,10 @@ _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "p
              "pt_adaptive_obj_reset", "pt_adaptive_obj_update", "pt_adaptive_obj_select", "pt_adaptive_obj_set_mask",
              "pt_adaptive_obj_apply", "pt_adaptive_obj_resolve", "pt_adaptive_obj_get", "pt_adaptive_enable",
              "pt_adaptive_update", "pt_adaptive_select", "pt_adaptive_set_mask", "pt_adaptive_info", "pt_adaptive_get",
-             "pt_adaptive_image"}
+             "pt_adaptive_image",
+             "pt_jpeg_params_default", "pt_jpeg_enc_create", "pt_jpeg_enc_destroy", "pt_jpeg_enc_bound", "pt_jpeg_enc_header",
+             "pt_jpeg_enc_pixels", "pt_jpeg_enc_accum", "pt_jpeg_encode_host", "pt_preview_jpeg", "pt_jpeg_enc_profile",
+             "pt_jpeg_enc_profile_read"}
 
 
 def lib() -> C.CDLL:

@@ -394,4 +394,20 @@ int pt_temporal_frame_ctx(pt_temporal* t, pt_ctx* ctx, float samples, void* stre
     return mark_ctx(c, st);
 }
 
+// ---- preview frames as JPEG ---------------------------------------------------
+// pt_preview_rgba's ordering and division by iter, the bytes going straight into the encoder's blocks
+// kernel: no RGBA plane is written.
+int pt_preview_jpeg(pt_ctx* ctx, int32_t iter, pt_jpeg_enc* e, uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream) {
+    CtxHead* c = ctx_head(ctx);
+    if (!c || !e || !d_out || !d_size || iter <= 0) return pt::fail(PT_ERR_ARG, "bad argument");
+    int32_t ew = 0, eh = 0;
+    if (int rc = pt::jpeg_enc_size(e, &ew, &eh)) return rc;
+    if (ew != c->W || (int64_t)ew * eh != (int64_t)c->npix)
+        return pt::fail(PT_ERR_ARG, "the JPEG encoder and the context's tile differ in size");
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = wait_finalize(c, st)) return rc;
+    if (int rc = pt_jpeg_enc_accum(e, c->image, (float)iter, d_out, cap, d_size, st)) return rc;
+    return mark_ctx(c, st);
+}
+
 }  // extern "C"

@@ -69,6 +69,8 @@ int adaptive_update_check(const pt_adaptive* a, float batch_samples);
 int temporal_case(const pt_temporal* t, const pt_camera* cam, float samples);
 int temporal_staging(pt_temporal* t, int kind, float** gA, float** gB, float** alb);
 int temporal_size(const pt_temporal* t, int32_t* width, int32_t* height);
+// pt_jpeg_enc (pt_jpeg_enc.hip): the image size an encoder was created for
+int jpeg_enc_size(const pt_jpeg_enc* e, int32_t* width, int32_t* height);
 
 inline float bits_to_float(int32_t v) {
     float f;

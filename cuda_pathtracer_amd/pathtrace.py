@@ -20,7 +20,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._native import AdaptiveParams, DenoiseParams, DenoiseVarParams, TemporalParams, check_pt, lib  # noqa: F401
+from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, JpegParams, TemporalParams, check_pt,  # noqa: F401
+                      lib)
 
 SPHERE, CUBE, MESH = 0, 1, 2
 
@@ -420,6 +421,14 @@ class PathTracer:
     def preview_rgba(self, iteration: int, dst_ptr: int, stream=None) -> None:
         check_pt(lib().pt_preview_rgba(self._h, int(iteration), C.c_void_p(dst_ptr), _stream_ptr(stream)))
 
+    def preview_jpeg(self, iteration: int, encoder: "JpegEncoder", stream=None) -> bytes:
+        """The accumulated image of `iteration` iterations as preview_rgba converts it, as a JPEG file
+        encoded on the device by `encoder` (pt_preview_jpeg): only the file crosses to the host."""
+        out, size = encoder._buffers()
+        check_pt(lib().pt_preview_jpeg(self._h, int(iteration), encoder._h, out.data_ptr(), encoder.cap, size.data_ptr(),
+                                       _stream_ptr(stream)))
+        return encoder._read(stream)
+
     def gbuffer(self) -> dict:
         """First-hit feature planes of the tile (pt_get_gbuffer; the deterministic camera ray): normal
         (rows, W, 3), mat (rows, W) int32 with -1 on a miss, position (rows, W, 3), t (rows, W) with -1
@@ -674,6 +683,113 @@ class TemporalHistory:
         check_pt(lib().pt_temporal_get(self._h, h0.ctypes.data, h1.ctypes.data, ga.ctypes.data, gb.ctypes.data,
                                        pv.ctypes.data, al.ctypes.data))
         return {"mean": h0[..., :3].copy(), "h": h0[..., 3].copy(), "mu": h1, "gA": ga, "gB": gb, "prev": pv, "albedo": al}
+
+
+def _jpeg_params(quality: int, subsampling, mirror_x: bool) -> "N.JpegParams":
+    sub = {"444": N.JPEG_444, "420": N.JPEG_420, N.JPEG_444: N.JPEG_444, N.JPEG_420: N.JPEG_420}.get(subsampling)
+    if sub is None:
+        raise ValueError(f"subsampling {subsampling!r}: '444' or '420'")
+    p = N.JpegParams.default()
+    p.quality, p.subsampling, p.mirror_x = int(quality), sub, int(bool(mirror_x))
+    return p
+
+
+class JpegEncoder:
+    """pt_jpeg_enc: a baseline JPEG encoder on the device for (height, width) images.
+    It owns its scratch and a device output buffer of `cap` bytes (default: `bound`, which every file
+    fits); params: a JpegParams (default: quality 90, 4:2:0)."""
+
+    def __init__(self, width: int, height: int, params: "N.JpegParams | None" = None, cap: int | None = None):
+        self.width, self.height = int(width), int(height)
+        self._h = C.c_void_p()
+        prm = params if params is not None else N.JpegParams.default()
+        check_pt(lib().pt_jpeg_enc_create(self.width, self.height, C.byref(prm), C.byref(self._h)))
+        self.bound = int(lib().pt_jpeg_enc_bound(self._h))
+        self.cap = self.bound if cap is None else int(cap)
+        self._out = self._size = None
+
+    def free(self) -> None:
+        if self._h is not None and self._h.value:
+            check_pt(lib().pt_jpeg_enc_destroy(self._h))
+        self._h = None
+        self._out = self._size = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def header(self) -> bytes:
+        """The file header SOI .. SOS (pt_jpeg_enc_header; no device needed)."""
+        n = int(lib().pt_jpeg_enc_header(self._h, None, 0))
+        buf = (C.c_uint8 * n)()
+        lib().pt_jpeg_enc_header(self._h, buf, n)
+        return bytes(buf)
+
+    def _buffers(self):
+        import torch
+        if self._out is None:
+            self._out = torch.empty(max(self.cap, 1), dtype=torch.uint8, device="cuda")
+            self._size = torch.zeros(1, dtype=torch.int64, device="cuda")
+        return self._out, self._size
+
+    def _read(self, stream) -> bytes:
+        """The size first, then that many bytes."""
+        import torch
+        if stream is not None:   # (a copy on torch's stream does not wait for another stream's encode)
+            (stream if hasattr(stream, "synchronize") else torch.cuda.ExternalStream(int(stream))).synchronize()
+        size = int(self._size.cpu()[0])
+        if size < 0:
+            raise N.PtError(1, f"the JPEG file needs {-size} bytes, the output buffer holds {self.cap}")
+        return self._out[:size].cpu().numpy().tobytes()
+
+    def encode(self, src, pixel_stride: int | None = None, samples: float | None = None, stream=None) -> bytes:
+        """One file.  src: an (H, W, 3 | 4) uint8 array or tensor (RGB8 / RGBA8, alpha ignored), or with
+        `samples` an (H, W, 3) float32 accumulator of that many samples; or a device pointer (int) to
+        either, pixels with their pixel_stride (3 or 4).  Asynchronous on `stream` up to the copy of the
+        size word and then the file's bytes."""
+        import torch
+        keep = None
+        if isinstance(src, int):
+            ptr = src
+            if samples is None and pixel_stride is None:
+                raise ValueError("a device pointer needs pixel_stride (pixels) or samples (an accumulator)")
+        else:
+            want = torch.float32 if samples is not None else torch.uint8
+            t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src))
+            chans = (3,) if samples is not None else (3, 4)
+            if t.dtype != want or t.dim() != 3 or tuple(t.shape[:2]) != (self.height, self.width) or t.shape[2] not in chans:
+                raise ValueError(f"source {tuple(t.shape)} {t.dtype}: expected ({self.height}, {self.width}, "
+                                 f"{' | '.join(map(str, chans))}) {want}")
+            keep = t.contiguous().cuda()
+            ptr, pixel_stride = keep.data_ptr(), int(t.shape[2])
+        out, size = self._buffers()
+        if samples is not None:
+            check_pt(lib().pt_jpeg_enc_accum(self._h, C.c_void_p(ptr), float(samples), out.data_ptr(), self.cap,
+                                             size.data_ptr(), _stream_ptr(stream)))
+        else:
+            check_pt(lib().pt_jpeg_enc_pixels(self._h, C.c_void_p(ptr), int(pixel_stride), out.data_ptr(), self.cap,
+                                              size.data_ptr(), _stream_ptr(stream)))
+        data = self._read(stream)
+        del keep
+        return data
+
+
+def encode_jpeg(rgb8: np.ndarray, quality: int = 90, subsampling="420", mirror_x: bool = False) -> bytes:
+    """An (H, W, 3 | 4) uint8 image as a baseline JPEG file, encoded on the device (pt_jpeg_encode_host)."""
+    img = np.ascontiguousarray(rgb8, dtype=np.uint8)
+    if img.ndim != 3 or img.shape[2] not in (3, 4):
+        raise ValueError(f"image shape {img.shape}: expected (H, W, 3 | 4)")
+    h, w = img.shape[:2]
+    prm = _jpeg_params(quality, subsampling, mirror_x)
+    m = 8 if prm.subsampling == N.JPEG_444 else 16
+    blocks = (3 if m == 8 else 6) * ((w + m - 1) // m) * ((h + m - 1) // m)
+    out = np.empty(623 + 2 * (blocks * 208) + 2, np.uint8)   # pt_jpeg_enc_bound
+    n = C.c_int64(0)
+    check_pt(lib().pt_jpeg_encode_host(w, h, img.ctypes.data, img.shape[2], C.byref(prm), out.ctypes.data, out.size,
+                                       C.byref(n)))
+    return out[:n.value].tobytes()
 
 
 def tonemap(image: np.ndarray, samples: float) -> np.ndarray:

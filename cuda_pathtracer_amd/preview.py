@@ -11,7 +11,10 @@ render process:
                    recompute is pt_scene_set_orbit, the PBO write is pt_preview_rgba.
   PreviewServer    the window: GET / (page: the image, mouse and keys, the panel), GET /frame.png
                    (the PBO as the window shows it), GET /state (title, panel text, settings),
-                   POST /event (GLFW-shaped input events and panel edits).
+                   POST /event (GLFW-shaped input events and panel edits).  With --jpeg QUALITY
+                   the frames are baseline JPEG files encoded on the device (pt_preview_jpeg,
+                   DESIGN.md §14): GET /frame.jpg, and GET /stream.mjpg, which pushes each new
+                   iteration's file once (multipart/x-mixed-replace).
 
     python -m cuda_pathtracer_amd.preview SCENE.json [--port 8080]   (then open the printed URL)
 
@@ -33,8 +36,8 @@ from pathlib import Path
 
 import numpy as np
 
-from .pathtrace import (DenoiseVarParams, GuiDataContainer, PathTracer, Scene, TemporalHistory, save_image,
-                        tonemap)
+from .pathtrace import (DenoiseVarParams, GuiDataContainer, JpegEncoder, PathTracer, Scene, TemporalHistory,
+                        _jpeg_params, encode_jpeg, save_image, tonemap)
 
 F32 = np.float32
 PI = F32(3.1415926535897932384626422832795028841971)   # utilities.h PI (a float)
@@ -59,10 +62,14 @@ class PreviewSession:
     tracer_factory(scene, gui) -> a PathTracer-like context (pathtraceInit); read_preview(ctx, it)
     -> the (H, W, 4) uint8 PBO contents for `it` accumulated iterations; history_factory(width, height)
     -> a TemporalHistory-like object (the `denoise_temporal` setting).  The defaults render on the
-    current HIP device; tests substitute them to drive the state machine on the CPU."""
+    current HIP device; tests substitute them to drive the state machine on the CPU.
+
+    jpeg: None (the default: frames are the RGBA PBO copied to the host), or a quality 1..100: the
+    session keeps a JpegEncoder and each frame is a JPEG file encoded on the device in the window's
+    orientation (jpeg_bytes); the PBO is then read only when display_rgb() asks for it."""
 
     def __init__(self, scene: Scene, gui: GuiDataContainer | None = None, out_dir: str | None = None,
-                 tracer_factory=None, read_preview=None, history_factory=None):
+                 tracer_factory=None, read_preview=None, history_factory=None, jpeg: int | None = None):
         self.scene = scene
         cam = scene.camera()
         self.width, self.height = int(cam.res[0]), int(cam.res[1])
@@ -107,7 +114,15 @@ class PreviewSession:
         # k samples, it is fed what that context accumulates from then on: (k, the accumulator at k, the
         # context's G-buffer, its camera), until the next context starts (None: the whole accumulator).
         self._history_base = None
+        self.jpeg = None if jpeg is None else int(jpeg)
+        if self.jpeg is not None and not 1 <= self.jpeg <= 100:
+            raise ValueError(f"jpeg quality {jpeg!r}: 1..100")
+        self._enc = None
+        self.jpeg_bytes = b""        # the current frame's file (JPEG mode)
+        self.frame_serial = 0        # counts the files: /stream.mjpg sends each once
+        self._rgba_current = True    # self.rgba holds the current frame (JPEG mode reads it on demand)
         self.lock = threading.RLock()
+        self.frame_ready = threading.Condition(self.lock)   # notified after every run_cuda
 
     # ---- callbacks (main.cpp:189-271) --------------------------------------------------------
     def key(self, key: str) -> None:
@@ -215,12 +230,21 @@ class PreviewSession:
                     self.rgba = self._temporal_preview()
                 elif self.denoise or self.denoise_variance:
                     self.rgba = self._denoised_preview()
+                elif self.jpeg is not None:   # only the file crosses to the host
+                    self.jpeg_bytes = self._jpeg_preview()
+                    self._rgba_current = False
                 else:
                     self.rgba = self._read(self.ctx, self.iteration)
+                if self.jpeg is not None and self._rgba_current:   # (a host array: the denoised paths)
+                    self.jpeg_bytes = encode_jpeg(self.rgba, self.jpeg, "420", mirror_x=True)
+                if self.jpeg is not None:
+                    self.frame_serial += 1
             else:
                 self.save_image()
+                self._current_rgba()
                 self._free()
                 self.done = True
+            self.frame_ready.notify_all()
             now = time.perf_counter()
             self._frame_times.append(now - (self._last_frame if self._last_frame is not None else t0))
             self._last_frame = now
@@ -231,6 +255,17 @@ class PreviewSession:
             self._dbuf = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device="cuda")
         ctx.preview_rgba(it, self._dbuf.data_ptr())   # (the render's stream: NULL)
         return self._dbuf.cpu().numpy()
+
+    def _jpeg_preview(self) -> bytes:
+        if self._enc is None:
+            self._enc = JpegEncoder(self.width, self.height, _jpeg_params(self.jpeg, "420", True))
+        return self.ctx.preview_jpeg(self.iteration, self._enc)
+
+    def _current_rgba(self) -> None:
+        """JPEG mode: the PBO of the current frame, read when something asks for it."""
+        if not self._rgba_current and self.ctx is not None:
+            self.rgba = self._read(self.ctx, self.iteration)
+        self._rgba_current = True
 
     def _denoised_preview(self) -> np.ndarray:
         """The PBO contents of the denoised image: the tonemapped bytes, un-mirrored back into the
@@ -243,6 +278,7 @@ class PreviewSession:
         return self._pbo_of(img)
 
     def _pbo_of(self, img: np.ndarray) -> np.ndarray:
+        self._rgba_current = True
         rgb = tonemap(img, 1.0)[:, ::-1]
         out = np.zeros((self.height, self.width, 4), np.uint8)
         out[..., :3] = rgb
@@ -288,9 +324,14 @@ class PreviewSession:
 
     def close(self) -> None:
         with self.lock:
+            self._current_rgba()
             self._free()
             self._free_history()
             self._dbuf = None
+            if self._enc is not None:
+                self._enc.free()
+                self._enc = None
+            self.frame_ready.notify_all()
 
     # ---- what the window shows ----------------------------------------------------------------
     def title(self) -> str:   # preview.cpp:297
@@ -300,6 +341,7 @@ class PreviewSession:
         """The window's pixels: the PBO through the quad's texture coordinates (preview.cpp:43-68:
         u = 1 at the left edge, v = 0 at the top), i.e. x mirrored, rows top-down."""
         with self.lock:
+            self._current_rgba()
             return np.ascontiguousarray(self.rgba[:, ::-1, :3])
 
     def state(self) -> dict:
@@ -400,8 +442,12 @@ poll();</script></body></html>"""
 class PreviewServer:
     """The window: a render loop thread (preview.cpp:289-322's mainLoop) and an HTTP server."""
 
-    def __init__(self, session: PreviewSession, host: str = "127.0.0.1", port: int = 0):
+    def __init__(self, session: PreviewSession, host: str = "127.0.0.1", port: int = 0, jpeg: int | None = None):
         self.session = session
+        if jpeg is not None:
+            if not 1 <= int(jpeg) <= 100:
+                raise ValueError(f"jpeg quality {jpeg!r}: 1..100")
+            session.jpeg = int(jpeg)
         self._stop = threading.Event()
         self._png = (-1, b"")   # (iteration, bytes) of the last encoded frame
         srv = self
@@ -420,14 +466,41 @@ class PreviewServer:
 
             def do_GET(self):  # noqa: N802
                 path = self.path.split("?", 1)[0]
+                jpeg = srv.session.jpeg is not None
                 if path == "/":
-                    self._send(200, _PAGE.encode(), "text/html; charset=utf-8")
+                    page = _PAGE.replace("/frame.png", "/frame.jpg") if jpeg else _PAGE
+                    self._send(200, page.encode(), "text/html; charset=utf-8")
                 elif path == "/frame.png":
                     self._send(200, srv.frame_png(), "image/png")
+                elif path == "/frame.jpg" and jpeg:
+                    self._send(200, srv.frame_jpeg()[1], "image/jpeg")
+                elif path == "/stream.mjpg" and jpeg:
+                    self._stream()
                 elif path == "/state":
                     self._send(200, json.dumps(srv.session.state()).encode(), "application/json")
                 else:
                     self._send(404, b"not found", "text/plain")
+
+            def _stream(self) -> None:
+                """Each new iteration's file once, as multipart/x-mixed-replace, until the window closes."""
+                self.send_response(200)
+                self.send_header("Content-Type", "multipart/x-mixed-replace; boundary=frame")
+                self.send_header("Cache-Control", "no-store")
+                self.end_headers()
+                ses, shown = srv.session, 0
+                try:
+                    while True:
+                        with ses.frame_ready:
+                            while ses.frame_serial == shown:
+                                if srv._stop.is_set() or ses.should_close or ses.done:
+                                    return
+                                ses.frame_ready.wait(0.25)
+                            shown, it, data = ses.frame_serial, ses.iteration, ses.jpeg_bytes
+                        self.wfile.write(b"--frame\r\nContent-Type: image/jpeg\r\nContent-Length: %d\r\nX-Iteration: %d\r\n\r\n"
+                                         % (len(data), it) + data + b"\r\n")
+                        self.wfile.flush()
+                except (BrokenPipeError, ConnectionResetError):
+                    pass
 
             def do_POST(self):  # noqa: N802
                 if self.path.split("?", 1)[0] != "/event":
@@ -456,6 +529,12 @@ class PreviewServer:
             if self._png[0] != it:
                 self._png = (it, png_bytes(s.display_rgb()))
             return self._png[1]
+
+    def frame_jpeg(self) -> tuple:
+        """(iteration, file) of the current frame (JPEG mode)."""
+        s = self.session
+        with s.lock:
+            return s.iteration, s.jpeg_bytes
 
     def _loop(self) -> None:
         try:
@@ -503,10 +582,12 @@ def main(argv=None) -> int:
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8080)
     ap.add_argument("--out-dir", default=".", help="where S / ESC / the last iteration save the PNG")
+    ap.add_argument("--jpeg", type=int, default=None, metavar="QUALITY",
+                    help="encode the frames as JPEG on the device (1..100); adds /frame.jpg and /stream.mjpg")
     a = ap.parse_args(argv)
     scene = Scene(a.scene)
     print(f"Reading scene from {a.scene} ...", flush=True)
-    srv = PreviewServer(PreviewSession(scene, out_dir=a.out_dir), a.host, a.port).start()
+    srv = PreviewServer(PreviewSession(scene, out_dir=a.out_dir, jpeg=a.jpeg), a.host, a.port).start()
     print(f"preview at {srv.url}  (Esc in the page saves and quits)", flush=True)
     srv.wait()
     srv.stop()

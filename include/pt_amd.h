@@ -636,6 +636,54 @@ int pt_adaptive_get(pt_ctx* c, float* h_m1, float* h_m2, float* h_prev_rgb, uint
                     uint8_t* h_hot);
 int pt_adaptive_image(pt_ctx* c, const pt_denoise_var_params* var_params, float* host_rgb, float* host_var);
 
+/* ---- baseline JPEG encoding on the device ------------------------------------ */
+/* A JFIF file (SOF0, 8-bit, YCbCr 4:4:4 or 4:2:0, the Annex K quantisation tables scaled by the IJG
+ * quality rule, the Annex K Huffman tables, one scan, no restart markers) of width x height pixels,
+ * encoded on the device in exactly defined int32 arithmetic: the bytes are a function of the input
+ * bytes.  mirror_x reads column W-1-x (saveImage's and the preview window's orientation).  The object
+ * needs no context; pt_jpeg_enc_create touches no device (argument errors, PT_ERR_ARG, are found before
+ * any device call) and the scratch, sized for the worst case, is allocated at the first encode; later
+ * encodes neither allocate nor synchronise.  Width and height in 1..65535 with blocks * 1664 < 2^31
+ * (blocks: 8x8 blocks of all components, the image padded to whole MCUs). */
+#define PT_JPEG_444 0
+#define PT_JPEG_420 1
+typedef struct pt_jpeg_params {
+    int32_t quality;      /* 1..100, default 90 */
+    int32_t subsampling;  /* default PT_JPEG_420 */
+    int32_t mirror_x;     /* default 0 */
+    int32_t reserved[5];
+} pt_jpeg_params;
+void pt_jpeg_params_default(pt_jpeg_params* p);
+typedef struct pt_jpeg_enc pt_jpeg_enc;
+int pt_jpeg_enc_create(int32_t width, int32_t height, const pt_jpeg_params* p, pt_jpeg_enc** out);
+int pt_jpeg_enc_destroy(pt_jpeg_enc* e);
+/* The largest file an encode can write: header (623) + 2 x (blocks * 1664 / 8) + 2.  No device. */
+int64_t pt_jpeg_enc_bound(const pt_jpeg_enc* e);
+/* Inspection (host only, used by the tests): the file header SOI .. SOS, built at creation.  Returns its
+ * length and copies min(length, cap) bytes. */
+int64_t pt_jpeg_enc_header(const pt_jpeg_enc* e, uint8_t* out, int64_t cap);
+/* Asynchronous on `stream`, device pointers (the caller orders the calls of one object).  d_pix: RGB8 or
+ * RGBA8, pixel_stride 3 or 4, alpha ignored.  d_rgb: the float accumulator of `samples` samples (finite,
+ * > 0), whose bytes are pt_preview_rgba's.  The file goes to d_out and its size to *d_size (8-byte
+ * aligned); a file that does not fit cap leaves the negated size it needs in *d_size, and no byte at or
+ * beyond d_out + cap is written. */
+int pt_jpeg_enc_pixels(pt_jpeg_enc* e, const uint8_t* d_pix, int32_t pixel_stride,
+                       uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream);
+int pt_jpeg_enc_accum(pt_jpeg_enc* e, const float* d_rgb, float samples,
+                      uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream);
+/* Host arrays, synchronous.  A file larger than cap: PT_ERR_ARG, the size it needs in *size. */
+int pt_jpeg_encode_host(int32_t width, int32_t height, const uint8_t* pix, int32_t pixel_stride,
+                        const pt_jpeg_params* p, uint8_t* out, int64_t cap, int64_t* size);
+/* The context's accumulated image of `iter` iterations as pt_preview_rgba converts it, encoded by `e`
+ * (whose size must be the tile's, PT_ERR_ARG otherwise).  Orders itself like pt_preview_rgba. */
+int pt_preview_jpeg(pt_ctx* c, int32_t iter, pt_jpeg_enc* e, uint8_t* d_out, int64_t cap,
+                    int64_t* d_size, void* stream);
+/* Stage timing of an encoder (scripts/jpeg_time.py): while on, an encode records events around its
+ * stages; read waits for the last encode and returns the milliseconds of blocks, count, scan, emit and
+ * stuffing. */
+int pt_jpeg_enc_profile(pt_jpeg_enc* e, int32_t on);
+int pt_jpeg_enc_profile_read(pt_jpeg_enc* e, float ms[5]);
+
 #ifdef __cplusplus
 }
 #endif
