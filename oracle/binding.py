@@ -165,11 +165,22 @@ _TEXTURES: dict = {}
 
 def load_texture(path):
     """Decoded texels by the oracle's own restatement of stb_image 2.06's JPEG decoder
-    (oracle/jpeg_oracle.py; the reference's Texture::load, sceneStructs.h:171-175).  Cached per path."""
+    (oracle/jpeg_oracle.py; the reference's Texture::load, sceneStructs.h:171-175).  Cached per path.
+    An 8-bit RGB file of a lossless format (PNG, BMP: stbi_load reads them too) is read with PIL: its
+    texels are the file's, whoever decodes it.  Other modes are refused, not converted."""
     from oracle import jpeg_oracle
     key = str(path)
     if key not in _TEXTURES:
-        px = jpeg_oracle.load(key)
+        with open(key, "rb") as f:
+            head = f.read(2)
+        if head == b"\xff\xd8":
+            px = jpeg_oracle.load(key)
+        else:
+            from PIL import Image
+            with Image.open(key) as im:
+                if im.mode != "RGB" or "transparency" in im.info:
+                    raise ValueError(f"texture {key}: only 8-bit RGB is read from a non-JPEG file")
+                px = np.asarray(im, dtype=np.uint8)
         _TEXTURES[key] = (px.shape[1], px.shape[0], px.shape[2], np.ascontiguousarray(px).reshape(-1))
     return _TEXTURES[key]
 

@@ -96,13 +96,26 @@ def mesh_first_hit_ref(tris, geoms, cam, dt=np.float64, mode="bvh", edge_eps=1e-
       * denoise_ref.geom_hit's rules for cubes and spheres apply;
       * use_bbox: a mesh geom's box test is within edge_eps of its threshold (Max of 0, min of Max).
     """
-    assert mode in ("bvh", "linear", "textbook")
-    assert not (use_bbox and mode != "linear")
     H, W = cam.res[1], cam.res[0]
-    eps = dt(FLT_EPSILON)
     with np.errstate(all="ignore"):
         d_all = R.camera_rays(cam, dt).reshape(-1, 3)
-        o = np.asarray(list(cam.position), dt)
+    res = mesh_hit_ref(tris, geoms, np.asarray(list(cam.position), dt), d_all, dt, mode, edge_eps, use_bbox, chunk)
+    return {k: val.reshape((H, W) + val.shape[1:]) for k, val in res.items()}
+
+
+def mesh_hit_ref(tris, geoms, o, d_all, dt=np.float64, mode="bvh", edge_eps=1e-3, use_bbox=False, chunk=256):
+    """mesh_first_hit_ref's closest hit for the rays (o, d_all[i]): d_all is (n, 3); o is one origin (3,)
+    shared by all rays or one per ray (n, 3).  Every elementwise operation is the same in both forms (a
+    shared origin broadcasts), so a shared origin gives the same numbers as one repeated per ray.
+    Returns mesh_first_hit_ref's dict with flat (n, ...) arrays."""
+    assert mode in ("bvh", "linear", "textbook")
+    assert not (use_bbox and mode != "linear")
+    eps = dt(FLT_EPSILON)
+    with np.errstate(all="ignore"):
+        d_all = np.asarray(d_all, dt).reshape(-1, 3)
+        o_all = np.asarray(o, dt).reshape(-1, 3)
+        per_ray = o_all.shape[0] != 1
+        assert not per_ray or o_all.shape == d_all.shape
         nr = d_all.shape[0]
         v = tris["v"].astype(dt)
         vn = tris["n"].astype(dt)
@@ -110,9 +123,8 @@ def mesh_first_hit_ref(tris, geoms, cam, dt=np.float64, mode="bvh", edge_eps=1e-
         tid = tris["id"].astype(np.int64)
         nt = len(tid)
         v0, e1, e2 = v[:, 0], v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]
-        s = o - v0                                           # (T, 3)
-        q = np.stack(_cross(_comps(s), _comps(e1)), -1)      # glm::cross(s, e1), ray-independent
-        e2q = _dot3(_comps(e2), _comps(q))
+        e1c = tuple(e1[:, k][None, :] for k in range(3))
+        e2c = tuple(e2[:, k][None, :] for k in range(3))
         area2 = np.sqrt(_dot3(_cross(_comps(e1), _comps(e2)), _cross(_comps(e1), _comps(e2))))
         cen = (v[:, 0] + v[:, 1] + v[:, 2]) / dt(3)
         rad = np.sqrt(((v - cen[:, None, :]) ** 2).sum(-1)).max(-1)
@@ -125,6 +137,7 @@ def mesh_first_hit_ref(tris, geoms, cam, dt=np.float64, mode="bvh", edge_eps=1e-
         for c0 in range(0, nr, chunk):
             d = d_all[c0:c0 + chunk]                          # (r, 3)
             r = d.shape[0]
+            o = o_all[c0:c0 + chunk] if per_ray else o_all    # (r, 3) or (1, 3)
             ob = np.broadcast_to(o, d.shape)
             risky = np.zeros(r, bool)
             best_t = np.full(r, np.inf, dt)
@@ -136,12 +149,15 @@ def mesh_first_hit_ref(tris, geoms, cam, dt=np.float64, mode="bvh", edge_eps=1e-
 
             if nt:
                 dc = tuple(d[:, k][:, None] for k in range(3))                 # (r, 1)
-                p = _cross(dc, tuple(e2[:, k][None, :] for k in range(3)))     # (r, T) x 3
-                a = _dot3(tuple(e1[:, k][None, :] for k in range(3)), p)
+                sc = tuple(o[:, k][:, None] - v0[:, k][None, :] for k in range(3))   # o - v0: (r, T) or (1, T)
+                q = _cross(sc, e1c)                                            # glm::cross(s, e1)
+                e2q = _dot3(e2c, q)
+                p = _cross(dc, e2c)                                            # (r, T) x 3
+                a = _dot3(e1c, p)
                 f = dt(1) / a
-                bx = f * _dot3(tuple(s[:, k][None, :] for k in range(3)), p)
-                by = f * _dot3(dc, tuple(q[:, k][None, :] for k in range(3)))
-                bz = f * e2q[None, :]
+                bx = f * _dot3(sc, p)
+                by = f * _dot3(dc, q)
+                bz = f * e2q
                 hit = ~(a < eps) & ~(bx < 0) & ~(bx > 1) & ~(by < 0) & ~(by + bx > 1) & (bz >= 0)
                 if mode == "linear":
                     hit &= bz > 0
@@ -159,8 +175,9 @@ def mesh_first_hit_ref(tris, geoms, cam, dt=np.float64, mode="bvh", edge_eps=1e-
                 m = np.minimum(np.minimum(bx, by), w)
                 front = a >= eps / 4
                 graze = np.abs(a) < dt(1e-3) * area2[None, :]
-                t_sph = _dot3(tuple((cen - o)[:, k][None, :] for k in range(3)), dc)      # closest approach
-                d2 = ((cen - o) ** 2).sum(-1)[None, :] - t_sph * t_sph
+                co = cen[None, :, :] - o[:, None, :]                                      # (r, T, 3) or (1, T, 3)
+                t_sph = _dot3(_comps(co), dc)                                             # closest approach
+                d2 = (co ** 2).sum(-1) - t_sph * t_sph
                 near_sph = (d2 <= (rad[None, :] + edge_eps) ** 2) & (t_sph + rad[None, :] >= 0)
                 met = front & ~graze & (m >= -edge_eps) & (bz >= -edge_eps)
                 bad = met & ((m < edge_eps) | (a < 4 * eps) | (np.abs(bz) < edge_eps))
@@ -232,8 +249,7 @@ def mesh_first_hit_ref(tris, geoms, cam, dt=np.float64, mode="bvh", edge_eps=1e-
             out["uv"].append(np.where(mesh_best[:, None], best_uv, dt(0)))
             out["keep"].append(~risky)
             out["back"].append(back)
-    res = {k: np.concatenate(val) for k, val in out.items()}
-    return {k: val.reshape((H, W) + val.shape[1:]) for k, val in res.items()}
+    return {k: np.concatenate(val) for k, val in out.items()}
 
 
 def geom_of_triangle(tri_id, geoms):

@@ -2,7 +2,7 @@
 
 * Known-answer vectors from the reference: stream_compaction/INSTRUCTION.md:262-302.
 * Independent restatements: numpy cumsum (scan), boolean masks (compaction, stable partition),
-  a pure-Python minstd_rand + utilhash (pathtrace.cu:57-62, intersections.h:13-22) checked against
+  a pure-Python minstd_rand + utilhash (tests/rng_ref.py; pathtrace.cu:57-62, intersections.h:13-22) checked against
   the C++ standard's minstd_rand value (10000th output from seed 1 == 399268537), numpy sin/cos
   and a float64 glm-order matrix composition (utilities.cpp:84-92).
 * Committed golden fixtures (tests/golden/*.npz, made by tests/golden/make_golden.py) freeze
@@ -12,12 +12,16 @@
 from __future__ import annotations
 
 import math
+import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 from oracle import binding as O
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+from rng_ref import M31, py_u01, u01_table  # noqa: E402
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 SCENES = Path(__file__).resolve().parent / "scenes"
@@ -71,30 +75,6 @@ def test_scan_compact_golden():
 
 
 # ---- RNG -----------------------------------------------------------------------------------
-M31 = 2147483647
-
-
-def utilhash(a: int) -> int:
-    m = 0xFFFFFFFF
-    a = ((a + 0x7ed55d16) + (a << 12)) & m
-    a = ((a ^ 0xc761c23c) ^ (a >> 19)) & m
-    a = ((a + 0x165667b1) + (a << 5)) & m
-    a = ((a + 0xd3a2646c) ^ (a << 9)) & m
-    a = ((a + 0xfd7046c5) + (a << 3)) & m
-    a = ((a ^ 0xb55a4f09) ^ (a >> 16)) & m
-    return a
-
-
-def py_u01(it: int, index: int, depth: int, count: int) -> np.ndarray:
-    h = utilhash((1 << 31) | (depth << 22) | it) ^ utilhash(index)
-    x = h % M31 or 1
-    out = []
-    for _ in range(count):
-        x = (48271 * x) % M31
-        out.append(np.float32(x - 1) * np.float32(2.0 ** -31))
-    return np.array(out, np.float32)
-
-
 def test_minstd_standard_check_value():
     x = 1
     for _ in range(10000):
@@ -109,6 +89,12 @@ def test_rng_matches_python_restatement_and_golden():
         np.testing.assert_array_equal(got, py_u01(it, index, depth, 16))
         np.testing.assert_array_equal(got, ref)
         assert (got >= 0).all() and (got < 1).all()
+    # the vectorised form tests/path_ref.py draws from: one row per index, equal to the scalar form
+    idx = np.array([0, 1, 47, 1727, 65535, 2 ** 31 - 1])
+    for it, depth in ((1, 8), (7, 1), (123456, 3)):
+        tab = u01_table(it, idx, depth, 6)
+        for i, row in zip(idx.tolist(), tab):
+            np.testing.assert_array_equal(row, py_u01(it, i, depth, 6))
 
 
 # ---- math ------------------------------------------------------------------------------------
