@@ -134,6 +134,24 @@ class JpegParams(C.Structure):
 
 JPEG_444, JPEG_420 = 0, 1   # PT_JPEG_*
 assert C.sizeof(JpegParams) == 32
+
+
+class PngParams(C.Structure):
+    """pt_png_params; PngParams.default() = pt_png_params_default (adaptive filter, 32 KiB deflate blocks,
+    the preview's conversion, no mirror)."""
+    _fields_ = [("filter", C.c_int32), ("block_bytes", C.c_int32), ("conv", C.c_int32), ("mirror_x", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+    @classmethod
+    def default(cls) -> "PngParams":
+        p = cls()
+        lib().pt_png_params_default(C.byref(p))
+        return p
+
+
+PNG_FILTER_ADAPTIVE = 5                  # PT_PNG_FILTER_ADAPTIVE
+PNG_CONV_PREVIEW, PNG_CONV_SAVE = 0, 1   # PT_PNG_CONV_*
+assert C.sizeof(PngParams) == 32
 assert C.sizeof(DenoiseParams) == 32 and C.sizeof(DenoiseVarParams) == 32 and C.sizeof(TemporalParams) == 32
 assert C.sizeof(AdaptiveParams) == 32
 assert C.sizeof(Geom) == 272 and C.sizeof(Material) == 48 and C.sizeof(Triangle) == 124
@@ -296,6 +314,16 @@ SIGNATURES = {
     "pt_preview_jpeg": (_I, [_P, _I, _P, _P, C.c_int64, _P, _P]),
     "pt_jpeg_enc_profile": (_I, [_P, _I]),
     "pt_jpeg_enc_profile_read": (_I, [_P, _FP]),
+    "pt_png_params_default": (None, [C.POINTER(PngParams)]),
+    "pt_png_enc_create": (_I, [_I, _I, C.POINTER(PngParams), C.POINTER(_P)]),
+    "pt_png_enc_destroy": (_I, [_P]),
+    "pt_png_enc_bound": (C.c_int64, [_P]),
+    "pt_png_enc_pixels": (_I, [_P, _P, _I, _P, C.c_int64, _P, _P]),
+    "pt_png_enc_accum": (_I, [_P, _P, _F, _P, C.c_int64, _P, _P]),
+    "pt_png_encode_host": (_I, [_I, _I, _P, _I, C.POINTER(PngParams), _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "pt_preview_png": (_I, [_P, _I, _P, _P, C.c_int64, _P, _P]),
+    "pt_png_enc_profile": (_I, [_P, _I]),
+    "pt_png_enc_profile_read": (_I, [_P, _FP]),
 }
 
 _lib = None
@@ -317,7 +345,8 @@ def _preload_torch() -> None:
 # variance entry points, pt_temporal_* and pt_adaptive_*: the A/B against the builds before them;
 # pt_ctx_depart_counts: the A/B against the build before the room's departure claim;
 # pt_ctx_exact_counts, pt_selftest_exact: the A/B against the build before the exact tests' single gate;
-# pt_jpeg_*, pt_preview_jpeg: the A/B against the build before the JPEG encoder).
+# pt_jpeg_*, pt_preview_jpeg: the A/B against the build before the JPEG encoder; pt_png_*, pt_preview_png: the
+# A/B against the build before the PNG encoder).
 _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
              "pt_ctx_exact_counts", "pt_selftest_exact",
              "pt_moments_create",
@@ -334,7 +363,9 @@ _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "p
              "pt_adaptive_image",
              "pt_jpeg_params_default", "pt_jpeg_enc_create", "pt_jpeg_enc_destroy", "pt_jpeg_enc_bound", "pt_jpeg_enc_header",
              "pt_jpeg_enc_pixels", "pt_jpeg_enc_accum", "pt_jpeg_encode_host", "pt_preview_jpeg", "pt_jpeg_enc_profile",
-             "pt_jpeg_enc_profile_read"}
+             "pt_jpeg_enc_profile_read",
+             "pt_png_params_default", "pt_png_enc_create", "pt_png_enc_destroy", "pt_png_enc_bound", "pt_png_enc_pixels",
+             "pt_png_enc_accum", "pt_png_encode_host", "pt_preview_png", "pt_png_enc_profile", "pt_png_enc_profile_read"}
 
 
 def lib() -> C.CDLL:

@@ -28,7 +28,7 @@ ARCH = "gfx950"
 # correctly-rounded operations unless the source writes fmaf(); keeps GPU == oracle bitwise.
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 DEVICE_SRCS = ["sc_kernels.hip", "sc_variants.hip", "pt_kernels.hip", "bvh_build.hip", "pt_denoise.hip",
-               "pt_temporal.hip", "pt_adaptive.hip", "pt_jpeg_enc.hip"]
+               "pt_temporal.hip", "pt_adaptive.hip", "pt_jpeg_enc.hip", "pt_png_enc.hip"]
 # pt_kernels.hip: no SLP vectorisation.  Packing independent f32 ops into v_pk_* pairs needed
 # register pairs and moves: k_bounce took 79 VGPRs (6 waves/SIMD) instead of 60 (8 waves), and
 # measured 30.8k vs 32.7k Mray/s on the bench (same box, alternating runs; same bits).
@@ -187,6 +187,21 @@ def build_trav_stats(verbose: bool = False, force: bool = False) -> Path:
         _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(TRAV_LIB), str(obj),
               *map(str, others), "-lz"], verbose)
     return TRAV_LIB
+
+
+def build_png_chunk_variant(chunk: int = 1024, verbose: bool = False) -> Path:
+    """Measurement library (not the product): pt_png_enc.hip with another lane chunk size C (-DPT_PNG_CHUNK; 512 or
+    1024), as build/libpt_amd_png_c<chunk>.so, which PT_AMD_LIB selects for scripts/png_time.py --grid-only: the C
+    column of the grid behind the encoder's defaults.  Its files differ from the definition's."""
+    build_native(verbose)
+    objdir = PKG / "build"
+    obj = objdir / f"pt_png_enc_c{chunk}.o"
+    out = objdir / f"libpt_amd_png_c{chunk}.so"
+    _run([HIPCC, "-x", "hip", f"--offload-arch={ARCH}", *COMMON, f"-DPT_PNG_CHUNK={chunk}", "-I", str(ROOT / "include"),
+          "-c", str(CSRC / "pt_png_enc.hip"), "-o", str(obj)], verbose)
+    _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(out), str(obj),
+          *map(str, other_objs("pt_png_enc.hip")), "-lz"], verbose)
+    return out
 
 
 def build_all(verbose: bool = False, force: bool = False) -> None:

@@ -410,4 +410,20 @@ int pt_preview_jpeg(pt_ctx* ctx, int32_t iter, pt_jpeg_enc* e, uint8_t* d_out, i
     return mark_ctx(c, st);
 }
 
+// ---- frames and final images as PNG -------------------------------------------
+// The same ordering; the encoder's filter kernel converts the accumulator as its params.conv says.
+int pt_preview_png(pt_ctx* ctx, int32_t iter, pt_png_enc* e, uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream) {
+    CtxHead* c = ctx_head(ctx);
+    if (!c || !e || !d_out || !d_size || iter <= 0) return pt::fail(PT_ERR_ARG, "bad argument");
+    if (c->world > 1) return pt::fail(PT_ERR_ARG, "pt_preview_png needs the whole image (world == 1)");
+    int32_t ew = 0, eh = 0;
+    if (int rc = pt::png_enc_size(e, &ew, &eh)) return rc;
+    if (ew != c->W || (int64_t)ew * eh != (int64_t)c->npix)
+        return pt::fail(PT_ERR_ARG, "the PNG encoder and the context's tile differ in size");
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = wait_finalize(c, st)) return rc;
+    if (int rc = pt_png_enc_accum(e, c->image, (float)iter, d_out, cap, d_size, st)) return rc;
+    return mark_ctx(c, st);
+}
+
 }  // extern "C"

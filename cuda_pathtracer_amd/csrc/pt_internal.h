@@ -71,6 +71,8 @@ int temporal_staging(pt_temporal* t, int kind, float** gA, float** gB, float** a
 int temporal_size(const pt_temporal* t, int32_t* width, int32_t* height);
 // pt_jpeg_enc (pt_jpeg_enc.hip): the image size an encoder was created for
 int jpeg_enc_size(const pt_jpeg_enc* e, int32_t* width, int32_t* height);
+// pt_png_enc (pt_png_enc.hip): the same
+int png_enc_size(const pt_png_enc* e, int32_t* width, int32_t* height);
 
 inline float bits_to_float(int32_t v) {
     float f;

@@ -4,7 +4,9 @@
 // pathtraceFree().  The camera is the first-frame orbit recompute (done by pt_scene_finalize).
 //
 //   pathtracer_amd SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise]
-//                  [--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K]
+//                  [--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png]
+// --device-png writes the final PNG on the device (pt_preview_png with pt_tonemap's conversion and the x
+// mirror: the same name and the same pixels, another file; only the file crosses to the host).
 // --denoise also writes the a-trous-filtered image (pt_denoise_image) as ...samp.denoised.png (and
 // .denoised.hdr with --hdr); --denoise-variance tracks the per-pixel variance (pt_track_variance, one
 // pt_variance_update per iteration; the raw image is the same) and writes the variance-guided filter's
@@ -56,6 +58,36 @@ std::string saveImage(const Scene& scene, const std::string& dir, const std::str
         std::fprintf(stderr, "saveImage: %s\n", pt_last_error());
         std::exit(EXIT_FAILURE);
     }
+    return filename;
+}
+
+// --device-png: saveImage's file name and pixels, the file written by the device encoder.
+std::string saveImageDevice(const Scene& scene, const std::string& dir, const std::string& start, int iteration) {
+    std::ostringstream ss;
+    ss << scene.state.imageName << "." << start << "." << (float)iteration << "samp";
+    std::string filename = (dir.empty() ? std::string() : dir + "/") + ss.str() + ".png";
+    auto die = [](const char* what, const char* why) {
+        std::fprintf(stderr, "saveImage (device): %s: %s\n", what, why);
+        std::exit(EXIT_FAILURE);
+    };
+    pt_png_params prm;
+    pt_png_params_default(&prm);
+    prm.conv = PT_PNG_CONV_SAVE;
+    prm.mirror_x = 1;
+    pt_png_enc* enc = nullptr;
+    if (pt_png_enc_create(scene.state.camera.res[0], scene.state.camera.res[1], &prm, &enc)) die("encoder", pt_last_error());
+    const int64_t cap = pt_png_enc_bound(enc);
+    uint8_t* d = nullptr;   // size word | file
+    if (hipMalloc((void**)&d, 256 + (size_t)cap) != hipSuccess) die("hipMalloc", "out of device memory");
+    if (pt_preview_png(pathtraceContext(), iteration, enc, d + 256, cap, (int64_t*)d, nullptr)) die("encode", pt_last_error());
+    int64_t size = 0;
+    if (hipMemcpy(&size, d, sizeof(size), hipMemcpyDeviceToHost) != hipSuccess || size <= 0) die("size", "copy failed");
+    std::vector<uint8_t> file((size_t)size);
+    if (hipMemcpy(file.data(), d + 256, (size_t)size, hipMemcpyDeviceToHost) != hipSuccess) die("file", "copy failed");
+    (void)hipFree(d);
+    pt_png_enc_destroy(enc);
+    FILE* f = std::fopen(filename.c_str(), "wb");
+    if (!f || std::fwrite(file.data(), 1, file.size(), f) != file.size() || std::fclose(f)) die("write", filename.c_str());
     return filename;
 }
 
@@ -164,13 +196,14 @@ int main(int argc, char** argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2) {
         std::printf("Usage: %s SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise] "
-                    "[--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K]\n", argv[0]);
+                    "[--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png]\n", argv[0]);
         return 1;
     }
     const char* sceneFile = argv[1];
     int iterations = -1;
     std::string out_dir, aov_dir;
     bool sort = false, png = true, hdr = false, denoise = false, denoise_var = false, aov = false, adaptive = false;
+    bool device_png = false;
     float adaptive_threshold = 0.0f;
     int adaptive_every = 4;
     for (int i = 2; i < argc; ++i) {
@@ -178,6 +211,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out_dir = argv[++i];
         else if (!std::strcmp(argv[i], "--sort")) sort = true;
         else if (!std::strcmp(argv[i], "--no-png")) png = false;
+        else if (!std::strcmp(argv[i], "--device-png")) device_png = true;
         else if (!std::strcmp(argv[i], "--hdr")) hdr = true;   // also write the saveHDR .hdr file
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
         else if (!std::strcmp(argv[i], "--denoise-variance")) denoise_var = true;
@@ -218,7 +252,9 @@ int main(int argc, char** argv) {
     (void)st;
     std::printf("rendered %d iteration(s) of %s (%dx%d, depth %d) in %.3f s\n", iteration, sceneFile,
                 scene->state.camera.res[0], scene->state.camera.res[1], scene->state.traceDepth, secs);
-    if (png) std::printf("wrote %s\n", saveImage(*scene, out_dir, startTimeString, iteration).c_str());
+    if (png)
+        std::printf("wrote %s\n", device_png ? saveImageDevice(*scene, out_dir, startTimeString, iteration).c_str()
+                                             : saveImage(*scene, out_dir, startTimeString, iteration).c_str());
     if (hdr) std::printf("wrote %s\n", saveImage(*scene, out_dir, startTimeString, iteration, true).c_str());
     if (denoise) {
         std::vector<float> dn((size_t)scene->state.camera.res[0] * scene->state.camera.res[1] * 3);

@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, JpegParams, TemporalParams, check_pt,  # noqa: F401
+from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, JpegParams, PngParams, TemporalParams, check_pt,  # noqa: F401
                       lib)
 
 SPHERE, CUBE, MESH = 0, 1, 2
@@ -429,6 +429,28 @@ class PathTracer:
                                        _stream_ptr(stream)))
         return encoder._read(stream)
 
+    def preview_png(self, iteration: int, encoder: "PngEncoder", stream=None) -> bytes:
+        """The accumulated image of `iteration` iterations as a PNG file written on the device by `encoder`
+        (pt_preview_png), converted as the encoder's params.conv says: only the file crosses to the host."""
+        out, size = encoder._buffers()
+        check_pt(lib().pt_preview_png(self._h, int(iteration), encoder._h, out.data_ptr(), encoder.cap, size.data_ptr(),
+                                      _stream_ptr(stream)))
+        return encoder._read(stream)
+
+    def save_png(self, path: str, iteration: int) -> str:
+        """saveImage's file written on the device: save_image's pixels (pt_tonemap's conversion, x-mirrored) of the
+        accumulator, without the accumulator crossing to the host."""
+        prm = N.PngParams.default()
+        prm.conv, prm.mirror_x = N.PNG_CONV_SAVE, 1
+        enc = PngEncoder(self.width, self.rows, prm)
+        try:
+            data = self.preview_png(iteration, enc)
+        finally:
+            enc.free()
+        with open(path, "wb") as f:
+            f.write(data)
+        return str(path)
+
     def gbuffer(self) -> dict:
         """First-hit feature planes of the tile (pt_get_gbuffer; the deterministic camera ray): normal
         (rows, W, 3), mat (rows, W) int32 with -1 on a miss, position (rows, W, 3), t (rows, W) with -1
@@ -699,6 +721,8 @@ class JpegEncoder:
     It owns its scratch and a device output buffer of `cap` bytes (default: `bound`, which every file
     fits); params: a JpegParams (default: quality 90, 4:2:0)."""
 
+    _kind = "jpeg"   # the entry points are pt_<kind>_enc_*
+
     def __init__(self, width: int, height: int, params: "N.JpegParams | None" = None, cap: int | None = None):
         self.width, self.height = int(width), int(height)
         self._h = C.c_void_p()
@@ -710,7 +734,7 @@ class JpegEncoder:
 
     def free(self) -> None:
         if self._h is not None and self._h.value:
-            check_pt(lib().pt_jpeg_enc_destroy(self._h))
+            check_pt(getattr(lib(), f"pt_{self._kind}_enc_destroy")(self._h))
         self._h = None
         self._out = self._size = None
 
@@ -741,7 +765,7 @@ class JpegEncoder:
             (stream if hasattr(stream, "synchronize") else torch.cuda.ExternalStream(int(stream))).synchronize()
         size = int(self._size.cpu()[0])
         if size < 0:
-            raise N.PtError(1, f"the JPEG file needs {-size} bytes, the output buffer holds {self.cap}")
+            raise N.PtError(1, f"the {self._kind.upper()} file needs {-size} bytes, the output buffer holds {self.cap}")
         return self._out[:size].cpu().numpy().tobytes()
 
     def encode(self, src, pixel_stride: int | None = None, samples: float | None = None, stream=None) -> bytes:
@@ -766,11 +790,11 @@ class JpegEncoder:
             ptr, pixel_stride = keep.data_ptr(), int(t.shape[2])
         out, size = self._buffers()
         if samples is not None:
-            check_pt(lib().pt_jpeg_enc_accum(self._h, C.c_void_p(ptr), float(samples), out.data_ptr(), self.cap,
-                                             size.data_ptr(), _stream_ptr(stream)))
+            check_pt(getattr(lib(), f"pt_{self._kind}_enc_accum")(self._h, C.c_void_p(ptr), float(samples), out.data_ptr(),
+                                                                  self.cap, size.data_ptr(), _stream_ptr(stream)))
         else:
-            check_pt(lib().pt_jpeg_enc_pixels(self._h, C.c_void_p(ptr), int(pixel_stride), out.data_ptr(), self.cap,
-                                              size.data_ptr(), _stream_ptr(stream)))
+            check_pt(getattr(lib(), f"pt_{self._kind}_enc_pixels")(self._h, C.c_void_p(ptr), int(pixel_stride), out.data_ptr(),
+                                                                   self.cap, size.data_ptr(), _stream_ptr(stream)))
         data = self._read(stream)
         del keep
         return data
@@ -789,6 +813,52 @@ def encode_jpeg(rgb8: np.ndarray, quality: int = 90, subsampling="420", mirror_x
     n = C.c_int64(0)
     check_pt(lib().pt_jpeg_encode_host(w, h, img.ctypes.data, img.shape[2], C.byref(prm), out.ctypes.data, out.size,
                                        C.byref(n)))
+    return out[:n.value].tobytes()
+
+
+class PngEncoder(JpegEncoder):
+    """pt_png_enc: a PNG encoder on the device for (height, width) images, with JpegEncoder's
+    encode(), bound, cap and free(); params: a PngParams (default: adaptive filter, 32 KiB deflate blocks)."""
+
+    _kind = "png"
+
+    def __init__(self, width: int, height: int, params: "N.PngParams | None" = None, cap: int | None = None):
+        self.width, self.height = int(width), int(height)
+        self._h = C.c_void_p()
+        self._out = self._size = None
+        prm = params if params is not None else N.PngParams.default()
+        check_pt(lib().pt_png_enc_create(self.width, self.height, C.byref(prm), C.byref(self._h)))
+        self.bound = int(lib().pt_png_enc_bound(self._h))
+        self.cap = self.bound if cap is None else int(cap)
+
+    def header(self) -> bytes:
+        raise NotImplementedError("a PNG file has no fixed header beyond the signature and IHDR")
+
+
+def _png_params(filter=None, block_bytes: int | None = None, conv: int | None = None, mirror_x: bool = False) -> "N.PngParams":
+    p = N.PngParams.default()
+    if filter is not None:
+        p.filter = int(filter)
+    if block_bytes is not None:
+        p.block_bytes = int(block_bytes)
+    if conv is not None:
+        p.conv = int(conv)
+    p.mirror_x = int(bool(mirror_x))
+    return p
+
+
+def encode_png(rgb8: np.ndarray, filter=None, block_bytes: int | None = None, mirror_x: bool = False) -> bytes:
+    """An (H, W, 3 | 4) uint8 image as an 8-bit RGB PNG file, written on the device (pt_png_encode_host)."""
+    img = np.ascontiguousarray(rgb8, dtype=np.uint8)
+    if img.ndim != 3 or img.shape[2] not in (3, 4):
+        raise ValueError(f"image shape {img.shape}: expected (H, W, 3 | 4)")
+    h, w = img.shape[:2]
+    prm = _png_params(filter, block_bytes, None, mirror_x)
+    n_f = h * (1 + 3 * w)
+    out = np.empty((9 * n_f + 10 * -(-n_f // max(prm.block_bytes, 1)) + 7) // 8 + 63, np.uint8)   # pt_png_enc_bound
+    n = C.c_int64(0)
+    check_pt(lib().pt_png_encode_host(w, h, img.ctypes.data, img.shape[2], C.byref(prm), out.ctypes.data, out.size,
+                                      C.byref(n)))
     return out[:n.value].tobytes()
 
 

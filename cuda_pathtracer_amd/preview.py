@@ -14,7 +14,9 @@ render process:
                    POST /event (GLFW-shaped input events and panel edits).  With --jpeg QUALITY
                    the frames are baseline JPEG files encoded on the device (pt_preview_jpeg,
                    DESIGN.md §14): GET /frame.jpg, and GET /stream.mjpg, which pushes each new
-                   iteration's file once (multipart/x-mixed-replace).
+                   iteration's file once (multipart/x-mixed-replace).  With --png-device
+                   /frame.png is written on the device too (pt_preview_png): the
+                   same pixels, another file.
 
     python -m cuda_pathtracer_amd.preview SCENE.json [--port 8080]   (then open the printed URL)
 
@@ -36,8 +38,8 @@ from pathlib import Path
 
 import numpy as np
 
-from .pathtrace import (DenoiseVarParams, GuiDataContainer, JpegEncoder, PathTracer, Scene, TemporalHistory,
-                        _jpeg_params, encode_jpeg, save_image, tonemap)
+from .pathtrace import (DenoiseVarParams, GuiDataContainer, JpegEncoder, PathTracer, PngEncoder, Scene, TemporalHistory,
+                        _jpeg_params, _png_params, encode_jpeg, encode_png, save_image, tonemap)
 
 F32 = np.float32
 PI = F32(3.1415926535897932384626422832795028841971)   # utilities.h PI (a float)
@@ -66,10 +68,16 @@ class PreviewSession:
 
     jpeg: None (the default: frames are the RGBA PBO copied to the host), or a quality 1..100: the
     session keeps a JpegEncoder and each frame is a JPEG file encoded on the device in the window's
-    orientation (jpeg_bytes); the PBO is then read only when display_rgb() asks for it."""
+    orientation (jpeg_bytes); the PBO is then read only when display_rgb() asks for it.
+
+    png_device: False (the default: /frame.png is png_bytes of the PBO, on the host), or True: the frame's
+    PNG is written on the device (png_frame: pt_preview_png for a raw frame, encode_png for the host arrays
+    of the denoised paths), with display_rgb()'s pixels; as in JPEG mode the PBO of a raw frame is read only
+    when display_rgb() asks for it."""
 
     def __init__(self, scene: Scene, gui: GuiDataContainer | None = None, out_dir: str | None = None,
-                 tracer_factory=None, read_preview=None, history_factory=None, jpeg: int | None = None):
+                 tracer_factory=None, read_preview=None, history_factory=None, jpeg: int | None = None,
+                 png_device: bool = False):
         self.scene = scene
         cam = scene.camera()
         self.width, self.height = int(cam.res[0]), int(cam.res[1])
@@ -118,6 +126,9 @@ class PreviewSession:
         if self.jpeg is not None and not 1 <= self.jpeg <= 100:
             raise ValueError(f"jpeg quality {jpeg!r}: 1..100")
         self._enc = None
+        self.png_device = bool(png_device)
+        self._png_enc = None
+        self._raw_frame = False      # the current frame is the context's accumulator as pt_preview_rgba converts it
         self.jpeg_bytes = b""        # the current frame's file (JPEG mode)
         self.frame_serial = 0        # counts the files: /stream.mjpg sends each once
         self._rgba_current = True    # self.rgba holds the current frame (JPEG mode reads it on demand)
@@ -233,8 +244,13 @@ class PreviewSession:
                 elif self.jpeg is not None:   # only the file crosses to the host
                     self.jpeg_bytes = self._jpeg_preview()
                     self._rgba_current = False
+                    self._raw_frame = True
+                elif self.png_device:          # /frame.png encodes from the accumulator: no RGBA copy per frame
+                    self._rgba_current = False
+                    self._raw_frame = True
                 else:
                     self.rgba = self._read(self.ctx, self.iteration)
+                    self._raw_frame = True
                 if self.jpeg is not None and self._rgba_current:   # (a host array: the denoised paths)
                     self.jpeg_bytes = encode_jpeg(self.rgba, self.jpeg, "420", mirror_x=True)
                 if self.jpeg is not None:
@@ -261,8 +277,20 @@ class PreviewSession:
             self._enc = JpegEncoder(self.width, self.height, _jpeg_params(self.jpeg, "420", True))
         return self.ctx.preview_jpeg(self.iteration, self._enc)
 
+    def png_frame(self) -> bytes:
+        """png_device: the current frame as a PNG file written on the device, display_rgb()'s pixels.  A raw
+        frame is encoded from the accumulator (only the file crosses to the host); a denoised or temporal
+        frame, and the last frame of a finished session, are host arrays and go through encode_png."""
+        with self.lock:
+            if self._raw_frame and self.ctx is not None and self.iteration > 0:
+                if self._png_enc is None:
+                    self._png_enc = PngEncoder(self.width, self.height, _png_params(mirror_x=True))
+                return self.ctx.preview_png(self.iteration, self._png_enc)
+            self._current_rgba()
+            return encode_png(self.rgba, mirror_x=True)
+
     def _current_rgba(self) -> None:
-        """JPEG mode: the PBO of the current frame, read when something asks for it."""
+        """JPEG mode and png_device: the PBO of the current frame, read when something asks for it."""
         if not self._rgba_current and self.ctx is not None:
             self.rgba = self._read(self.ctx, self.iteration)
         self._rgba_current = True
@@ -279,6 +307,7 @@ class PreviewSession:
 
     def _pbo_of(self, img: np.ndarray) -> np.ndarray:
         self._rgba_current = True
+        self._raw_frame = False
         rgb = tonemap(img, 1.0)[:, ::-1]
         out = np.zeros((self.height, self.width, 4), np.uint8)
         out[..., :3] = rgb
@@ -331,6 +360,9 @@ class PreviewSession:
             if self._enc is not None:
                 self._enc.free()
                 self._enc = None
+            if self._png_enc is not None:
+                self._png_enc.free()
+                self._png_enc = None
             self.frame_ready.notify_all()
 
     # ---- what the window shows ----------------------------------------------------------------
@@ -442,8 +474,11 @@ poll();</script></body></html>"""
 class PreviewServer:
     """The window: a render loop thread (preview.cpp:289-322's mainLoop) and an HTTP server."""
 
-    def __init__(self, session: PreviewSession, host: str = "127.0.0.1", port: int = 0, jpeg: int | None = None):
+    def __init__(self, session: PreviewSession, host: str = "127.0.0.1", port: int = 0, jpeg: int | None = None,
+                 png_device: bool | None = None):
         self.session = session
+        if png_device is not None:
+            session.png_device = bool(png_device)
         if jpeg is not None:
             if not 1 <= int(jpeg) <= 100:
                 raise ValueError(f"jpeg quality {jpeg!r}: 1..100")
@@ -527,7 +562,7 @@ class PreviewServer:
         with s.lock:
             it = s.iteration
             if self._png[0] != it:
-                self._png = (it, png_bytes(s.display_rgb()))
+                self._png = (it, s.png_frame() if s.png_device else png_bytes(s.display_rgb()))
             return self._png[1]
 
     def frame_jpeg(self) -> tuple:
@@ -584,10 +619,12 @@ def main(argv=None) -> int:
     ap.add_argument("--out-dir", default=".", help="where S / ESC / the last iteration save the PNG")
     ap.add_argument("--jpeg", type=int, default=None, metavar="QUALITY",
                     help="encode the frames as JPEG on the device (1..100); adds /frame.jpg and /stream.mjpg")
+    ap.add_argument("--png-device", action="store_true",
+                    help="write /frame.png on the device (pt_preview_png) instead of compressing the frame on the host")
     a = ap.parse_args(argv)
     scene = Scene(a.scene)
     print(f"Reading scene from {a.scene} ...", flush=True)
-    srv = PreviewServer(PreviewSession(scene, out_dir=a.out_dir, jpeg=a.jpeg), a.host, a.port).start()
+    srv = PreviewServer(PreviewSession(scene, out_dir=a.out_dir, jpeg=a.jpeg, png_device=a.png_device), a.host, a.port).start()
     print(f"preview at {srv.url}  (Esc in the page saves and quits)", flush=True)
     srv.wait()
     srv.stop()

@@ -684,6 +684,56 @@ int pt_preview_jpeg(pt_ctx* c, int32_t iter, pt_jpeg_enc* e, uint8_t* d_out, int
 int pt_jpeg_enc_profile(pt_jpeg_enc* e, int32_t on);
 int pt_jpeg_enc_profile_read(pt_jpeg_enc* e, float ms[5]);
 
+/* ---- PNG encoding on the device ---------------------------------------------- */
+/* An 8-bit RGB PNG (colour type 2, no interlace; signature, IHDR, one IDAT holding one zlib stream, IEND)
+ * of width x height pixels, written entirely by kernels: row filtering (a fixed type 0..4, or per row the
+ * type with the smallest sum of |signed residual|, ties to the lowest), literals and distance-1 matches
+ * within 512-byte lane chunks of the filtered stream, one deflate block per block_bytes coded with the
+ * fixed or a dynamic Huffman code (whichever is shorter, ties to fixed; no stored blocks), Adler-32 and
+ * CRC-32.  The bytes are a function of the input bytes.  mirror_x reads column W-1-x.  The object needs
+ * no context; pt_png_enc_create touches no device (argument errors, PT_ERR_ARG, are found before any
+ * device call) and the scratch, sized for the worst case, is allocated at the first encode; later encodes
+ * neither allocate nor synchronise.  Sizes whose stream bound 9 N + 10 blocks bits (N = H (1 + 3 W)) does
+ * not stay below 2^31 are refused. */
+#define PT_PNG_FILTER_ADAPTIVE 5
+#define PT_PNG_CONV_PREVIEW 0 /* pt_preview_rgba's bytes: (int)((double)(v / n) * 255.0), clamped */
+#define PT_PNG_CONV_SAVE 1    /* pt_tonemap's bytes: float division, clamp to 0..1, (uint8_t)(v * 255.f) */
+typedef struct pt_png_params {
+    int32_t filter;       /* 0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth, default PT_PNG_FILTER_ADAPTIVE */
+    int32_t block_bytes;  /* bytes of the filtered stream per deflate block: a multiple of 512 in
+                           * 1024..1048576, default 32768 */
+    int32_t conv;         /* how pt_png_enc_accum converts the accumulator, default PT_PNG_CONV_PREVIEW */
+    int32_t mirror_x;     /* default 0 */
+    int32_t reserved[4];
+} pt_png_params;
+void pt_png_params_default(pt_png_params* p);
+typedef struct pt_png_enc pt_png_enc;
+int pt_png_enc_create(int32_t width, int32_t height, const pt_png_params* p, pt_png_enc** out);
+int pt_png_enc_destroy(pt_png_enc* e);
+/* The largest file an encode can write: (9 N + 10 blocks + 7) / 8 + 63 bytes of framing.  No device. */
+int64_t pt_png_enc_bound(const pt_png_enc* e);
+/* Asynchronous on `stream`, device pointers (the caller orders the calls of one object).  d_pix: RGB8 or
+ * RGBA8, pixel_stride 3 or 4, alpha ignored.  d_rgb: the float accumulator of `samples` samples (finite,
+ * > 0), converted as params.conv says.  The file goes to d_out and its size to *d_size (8-byte aligned); a
+ * file that does not fit cap leaves the negated size it needs in *d_size, and no byte at or beyond
+ * d_out + cap is written. */
+int pt_png_enc_pixels(pt_png_enc* e, const uint8_t* d_pix, int32_t pixel_stride,
+                      uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream);
+int pt_png_enc_accum(pt_png_enc* e, const float* d_rgb, float samples,
+                     uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream);
+/* Host arrays, synchronous.  A file larger than cap: PT_ERR_ARG, the size it needs in *size. */
+int pt_png_encode_host(int32_t width, int32_t height, const uint8_t* pix, int32_t pixel_stride,
+                       const pt_png_params* p, uint8_t* out, int64_t cap, int64_t* size);
+/* The context's accumulated image divided by `iter`, encoded by `e` (whose size must be the tile's,
+ * PT_ERR_ARG otherwise; a sharded context, world > 1, is refused).  Orders itself like pt_preview_rgba. */
+int pt_preview_png(pt_ctx* c, int32_t iter, pt_png_enc* e, uint8_t* d_out, int64_t cap,
+                   int64_t* d_size, void* stream);
+/* Stage timing of an encoder (scripts/png_time.py): while on, an encode records events around its stages;
+ * read waits for the last encode and returns the milliseconds of filter, block codes and count, scan,
+ * zero and emit, checksums, and the output copy with the framing. */
+int pt_png_enc_profile(pt_png_enc* e, int32_t on);
+int pt_png_enc_profile_read(pt_png_enc* e, float ms[6]);
+
 #ifdef __cplusplus
 }
 #endif
