@@ -73,6 +73,24 @@ int read_back(CtxHead* c, const char* who, int rc, float* d, pt_denoiser* dn, st
     return PT_OK;
 }
 
+// The accumulator as a file of encoder `e` (of `iter` iterations), on the stream and behind the context's passes.
+// whole: the refusal of a context that renders one tile of several, or null.
+template <class Enc>
+int preview_file(pt_ctx* ctx, int32_t iter, Enc* e, int (*accum)(Enc*, const float*, float, uint8_t*, int64_t, int64_t*, void*),
+                 const char* name, const char* whole, uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream) {
+    CtxHead* c = ctx_head(ctx);
+    if (!c || !e || !d_out || !d_size || iter <= 0) return pt::fail(PT_ERR_ARG, "bad argument");
+    if (whole && c->world > 1) return pt::fail(PT_ERR_ARG, whole);
+    int32_t ew = 0, eh = 0;
+    pt::enc_size(pt::enc_head(e), &ew, &eh);
+    if (ew != c->W || (int64_t)ew * eh != (int64_t)c->npix)
+        return pt::fail(PT_ERR_ARG, std::string("the ") + name + " encoder and the context's tile differ in size");
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = wait_finalize(c, st)) return rc;
+    if (int rc = accum(e, c->image, (float)iter, d_out, cap, d_size, st)) return rc;
+    return mark_ctx(c, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -398,32 +416,14 @@ int pt_temporal_frame_ctx(pt_temporal* t, pt_ctx* ctx, float samples, void* stre
 // pt_preview_rgba's ordering and division by iter, the bytes going straight into the encoder's blocks
 // kernel: no RGBA plane is written.
 int pt_preview_jpeg(pt_ctx* ctx, int32_t iter, pt_jpeg_enc* e, uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream) {
-    CtxHead* c = ctx_head(ctx);
-    if (!c || !e || !d_out || !d_size || iter <= 0) return pt::fail(PT_ERR_ARG, "bad argument");
-    int32_t ew = 0, eh = 0;
-    if (int rc = pt::jpeg_enc_size(e, &ew, &eh)) return rc;
-    if (ew != c->W || (int64_t)ew * eh != (int64_t)c->npix)
-        return pt::fail(PT_ERR_ARG, "the JPEG encoder and the context's tile differ in size");
-    const hipStream_t st = (hipStream_t)stream;
-    if (int rc = wait_finalize(c, st)) return rc;
-    if (int rc = pt_jpeg_enc_accum(e, c->image, (float)iter, d_out, cap, d_size, st)) return rc;
-    return mark_ctx(c, st);
+    return preview_file(ctx, iter, e, pt_jpeg_enc_accum, "JPEG", nullptr, d_out, cap, d_size, stream);
 }
 
 // ---- frames and final images as PNG -------------------------------------------
 // The same ordering; the encoder's filter kernel converts the accumulator as its params.conv says.
 int pt_preview_png(pt_ctx* ctx, int32_t iter, pt_png_enc* e, uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream) {
-    CtxHead* c = ctx_head(ctx);
-    if (!c || !e || !d_out || !d_size || iter <= 0) return pt::fail(PT_ERR_ARG, "bad argument");
-    if (c->world > 1) return pt::fail(PT_ERR_ARG, "pt_preview_png needs the whole image (world == 1)");
-    int32_t ew = 0, eh = 0;
-    if (int rc = pt::png_enc_size(e, &ew, &eh)) return rc;
-    if (ew != c->W || (int64_t)ew * eh != (int64_t)c->npix)
-        return pt::fail(PT_ERR_ARG, "the PNG encoder and the context's tile differ in size");
-    const hipStream_t st = (hipStream_t)stream;
-    if (int rc = wait_finalize(c, st)) return rc;
-    if (int rc = pt_png_enc_accum(e, c->image, (float)iter, d_out, cap, d_size, st)) return rc;
-    return mark_ctx(c, st);
+    return preview_file(ctx, iter, e, pt_png_enc_accum, "PNG", "pt_preview_png needs the whole image (world == 1)", d_out, cap,
+                        d_size, stream);
 }
 
 }  // extern "C"

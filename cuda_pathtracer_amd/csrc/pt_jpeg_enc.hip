@@ -4,19 +4,19 @@
 // a function of the input bytes alone; tests/jpeg_enc_ref.py restates the definition in numpy integers and
 // the GPU tests compare byte for byte.
 //
-// Kernel shape: no inter-workgroup wait, no co-resident grid, no look-back; every prefix sum is the
-// three-kernel reduce / one-workgroup scan / apply of k_hist_*.
+// Kernel shape: no inter-workgroup wait, no co-resident grid, no look-back; the prefix sums, and the host side that
+// every encoder object has, are the shared unit's (pt_enc.h).
 //   k_jpeg_blocks   8 lanes per 8x8 block (lane = row, then lane = column), 32 blocks per workgroup: colour
 //                   conversion (the accumulator variant fuses k_preview's bytes), edge replication, 4:2:0
 //                   averaging (an MCU's Cb and Cr lanes split the row's pixels and swap halves), the row pass into LDS (transposed, block stride 72 words: conflict-free on
 //                   both sides), the column pass, quantisation, and the zigzag through LDS so that a lane
 //                   stores 16 contiguous bytes of the block's 128
 //   k_jpeg_count    one lane per block: the bit length of its code
-//   k_scan_*        exclusive scan of the bit lengths, in place
+//   scan            exclusive scan of the bit lengths, in place (pt::scan_exclusive_i32)
 //   k_jpeg_zero     the words of the unstuffed stream up to the total length
 //   k_jpeg_emit     one lane per block: the code assembled in a 64-bit register; words wholly inside the
 //                   block's bit range are stored, the first and last are ORed in (atomicOr)
-//   k_stuff_*       0xFF bytes per 4096-byte chunk (16 bytes per lane), their scan, and the stuffed bytes
+//   k_stuff_*       0xFF bytes per 4096-byte chunk (16 bytes per lane), their scan (pt::scan_tile_sums_i32), and the stuffed bytes
 //                   behind the header in the caller's buffer, then FF D9 and the size word
 #include <hip/hip_runtime.h>
 
@@ -26,7 +26,9 @@
 #include <string>
 #include <vector>
 
-#include "pt_internal.h"
+#include "pt_enc.h"
+
+using namespace pt;
 
 namespace {
 
@@ -34,9 +36,7 @@ constexpr int kHeaderBytes = 623;
 constexpr int kBlockBitsMax = 1664;   // 20 (DC) + 63 * 26 (AC)
 constexpr int kTile = 32;             // 8x8 blocks per workgroup of k_jpeg_blocks
 constexpr int kRowPad = 72;           // words per block of the row pass in LDS
-constexpr int kScanPer = 4, kScanTile = 256 * kScanPer;
 constexpr int kStuffChunk = 4096;     // bytes per workgroup of the stuffing kernels (16 per lane)
-constexpr int kMaxGrid = 1024;        // grid-stride kernels: workgroups at most
 constexpr int kStages = 5;            // blocks, count, scan, emit, stuff (pt_jpeg_enc_profile)
 
 // T[u][x] = round(2^13 s(u) cos((2x + 1) u pi / 16)), s(0) = sqrt(1/8), s(u) = 1/2
@@ -104,12 +104,6 @@ struct Geo {
 };
 
 // ---- blocks ---------------------------------------------------------------------------------------------
-// k_preview's byte of an accumulator value
-__device__ __forceinline__ int preview_byte(float v, float n) {
-    int q = (int)((double)(v / n) * 255.0);
-    return q < 0 ? 0 : (q > 255 ? 255 : q);
-}
-
 // The bytes of source pixel (x, y).
 template <bool ACC>
 __device__ __forceinline__ void rgb_at(const void* __restrict__ src, int stride, float n, int W, int x, int y, int& r,
@@ -356,79 +350,6 @@ __global__ __launch_bounds__(256) void k_jpeg_zero(uint32_t* __restrict__ stream
     for (int i = (int)blockIdx.x * 256 + (int)threadIdx.x; i < words; i += (int)gridDim.x * 256) stream[i] = 0u;
 }
 
-// ---- prefix sums ----------------------------------------------------------------------------------------
-// Exclusive scan of one value per lane over the workgroup (every lane calls it); *total: the workgroup's sum.
-__device__ __forceinline__ int block_excl_scan(int v, int* s_w, int* total) {
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();   // (s_w may still be read by the previous call)
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    int base = 0, sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int t = s_w[k];
-        if (k < wave) base += t;
-        sum += t;
-    }
-    *total = sum;
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(256) void k_scan_reduce(const int32_t* __restrict__ in, int n, int32_t* __restrict__ sums) {
-    __shared__ int s_w[4];
-    for (int tile = (int)blockIdx.x; tile * kScanTile < n; tile += (int)gridDim.x) {
-        const int base = tile * kScanTile + (int)threadIdx.x * kScanPer;
-        int v = 0, total;
-#pragma unroll
-        for (int k = 0; k < kScanPer; ++k) v += base + k < n ? in[base + k] : 0;
-        (void)block_excl_scan(v, s_w, &total);
-        if (threadIdx.x == 0) sums[tile] = total;
-    }
-}
-
-// One workgroup: the tile sums scanned in place, their total to *total_out.  With `bits` the number of tiles
-// is the stuffing kernels': the chunks of the (bits + 7) / 8 bytes of the unstuffed stream.
-__global__ __launch_bounds__(256) void k_scan_sums(int32_t* __restrict__ sums, int ntiles, const int32_t* __restrict__ bits,
-                                                    int32_t* __restrict__ total_out) {
-    __shared__ int s_w[4];
-    if (bits) ntiles = (((bits[0] + 7) >> 3) + kStuffChunk - 1) / kStuffChunk;
-    const int per = (ntiles + 255) / 256, j0 = (int)threadIdx.x * per;
-    int v = 0, total;
-    for (int j = j0; j < j0 + per && j < ntiles; ++j) v += sums[j];
-    int run = block_excl_scan(v, s_w, &total);
-    for (int j = j0; j < j0 + per && j < ntiles; ++j) {
-        const int a = sums[j];
-        sums[j] = run;
-        run += a;
-    }
-    if (threadIdx.x == 0) *total_out = total;
-}
-
-__global__ __launch_bounds__(256) void k_scan_apply(int32_t* __restrict__ io, int n, const int32_t* __restrict__ sums) {
-    __shared__ int s_w[4];
-    for (int tile = (int)blockIdx.x; tile * kScanTile < n; tile += (int)gridDim.x) {
-        const int base = tile * kScanTile + (int)threadIdx.x * kScanPer;
-        int x[kScanPer], v = 0, total;
-#pragma unroll
-        for (int k = 0; k < kScanPer; ++k) {
-            x[k] = base + k < n ? io[base + k] : 0;
-            v += x[k];
-        }
-        int run = block_excl_scan(v, s_w, &total) + sums[tile];
-#pragma unroll
-        for (int k = 0; k < kScanPer; ++k) {
-            if (base + k < n) io[base + k] = run;
-            run += x[k];
-        }
-    }
-}
-
 // ---- byte stuffing --------------------------------------------------------------------------------------
 // The lane's 16 bytes of the unstuffed stream (those below nbytes) and how many of them are 0xFF.
 __device__ __forceinline__ int stuff_load(const uint8_t* __restrict__ stream, int at, int nbytes, uint32_t (&w)[4]) {
@@ -442,10 +363,12 @@ __device__ __forceinline__ int stuff_load(const uint8_t* __restrict__ stream, in
     return cnt;
 }
 
+// *nchunks: the chunks of the unstuffed stream, for the scan of their sums.
 __global__ __launch_bounds__(256) void k_stuff_count(const uint8_t* __restrict__ stream, const int32_t* __restrict__ tot,
-                                                      int32_t* __restrict__ sums) {
+                                                      int32_t* __restrict__ sums, int32_t* __restrict__ nchunks) {
     __shared__ int s_w[4];
     const int nbytes = (tot[0] + 7) >> 3;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *nchunks = (nbytes + kStuffChunk - 1) / kStuffChunk;
     for (int tile = (int)blockIdx.x; tile * kStuffChunk < nbytes; tile += (int)gridDim.x) {
         uint32_t w[4];
         int total;
@@ -455,7 +378,7 @@ __global__ __launch_bounds__(256) void k_stuff_count(const uint8_t* __restrict__
     }
 }
 
-// tot[0]: the stream's bits; tot[1]: its 0xFF bytes.  Nothing at or beyond out + cap is written.
+// tot[0]: the stream's bits; tot[1]: its 0xFF bytes (tot[2]: k_stuff_count's chunks).  Nothing at or beyond out + cap is written.
 __global__ __launch_bounds__(256) void k_stuff_write(const uint8_t* __restrict__ stream, const int32_t* __restrict__ tot,
                                                       const int32_t* __restrict__ sums, const uint8_t* __restrict__ header,
                                                       uint8_t* __restrict__ out, long long cap, long long* __restrict__ size) {
@@ -489,13 +412,6 @@ __global__ __launch_bounds__(256) void k_stuff_write(const uint8_t* __restrict__
         *size = end + 2 <= cap ? end + 2 : -(end + 2);
     }
 }
-
-#define JE_TRY(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess)                                                               \
-            return pt::fail(PT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 // ---- host: tables and header ------------------------------------------------------------------------------
 void quant_table(const uint8_t (&base)[64], int quality, int32_t* out) {
@@ -553,38 +469,24 @@ void fill_tables(Tables& t, int32_t W, int32_t H, const pt_jpeg_params& p) {
     t.header[639] = (uint8_t)(h.size() == (size_t)kHeaderBytes);
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
-struct pt_jpeg_enc {
-    int32_t W = 0, H = 0;
+struct pt_jpeg_enc : EncHead {
+    pt_jpeg_enc() : EncHead("JPEG", "jpeg", kStages) {}
     pt_jpeg_params prm{};
     Geo geo{};
     int64_t worst = 0;                // bytes of the unstuffed stream at most: nblocks * 1664 / 8
     Tables tables{};
-    // The device side, one allocation made at the first encode: tables | coefficients | bit lengths, then
-    // offsets | unstuffed stream | the two scans' tile sums | totals (bits, 0xFF bytes).
-    uint8_t* dev = nullptr;
+    // The device side: tables | coefficients | bit lengths, then offsets | unstuffed stream | the two scans' tile
+    // sums | totals (bits, 0xFF bytes, stuffing chunks).
     Tables* d_tab = nullptr;
     int16_t* d_coef = nullptr;
     int32_t* d_len = nullptr;
     uint32_t* d_stream = nullptr;
     int32_t *d_sums1 = nullptr, *d_sums2 = nullptr, *d_tot = nullptr;
-    hipEvent_t ev = nullptr;          // after the last queued work (destroy waits for it)
-    bool ev_recorded = false;
-    bool profile = false;             // pt_jpeg_enc_profile: events around the stages of the last encode
-    hipEvent_t stage_ev[kStages + 1] = {};
 };
 
-namespace pt {
-int jpeg_enc_size(const pt_jpeg_enc* e, int32_t* width, int32_t* height) {
-    if (!e) return fail(PT_ERR_ARG, "null JPEG encoder");
-    *width = e->W;
-    *height = e->H;
-    return PT_OK;
-}
-}  // namespace pt
+const EncHead* pt::enc_head(const pt_jpeg_enc* e) { return e; }
 
 namespace {
 
@@ -611,34 +513,18 @@ int size_check(int32_t W, int32_t H, int32_t sub) {
 
 int je_alloc(pt_jpeg_enc* e) {
     if (e->dev) return PT_OK;
-    const size_t nb = (size_t)e->geo.nblocks;
-    const size_t o_tab = 0, o_coef = o_tab + align256(sizeof(Tables)), o_len = o_coef + align256(nb * 128),
-                 o_stream = o_len + align256(nb * 4), o_s1 = o_stream + align256((size_t)e->worst + 16),
-                 o_s2 = o_s1 + align256((nb / kScanTile + 1) * 4), o_tot = o_s2 + align256(((size_t)e->worst / kStuffChunk + 1) * 4),
-                 bytes = o_tot + 256;
-    if (hipMalloc((void**)&e->dev, bytes) != hipSuccess ||
-        (!e->ev && hipEventCreateWithFlags(&e->ev, hipEventDisableTiming) != hipSuccess)) {
-        if (e->dev) (void)hipFree(e->dev);
-        e->dev = nullptr;
-        (void)hipGetLastError();
-        return pt::fail(PT_ERR_NOMEM, "hipMalloc (JPEG encoder scratch)");
-    }
-    e->d_tab = (Tables*)(e->dev + o_tab);
-    e->d_coef = (int16_t*)(e->dev + o_coef);
-    e->d_len = (int32_t*)(e->dev + o_len);
-    e->d_stream = (uint32_t*)(e->dev + o_stream);
-    e->d_sums1 = (int32_t*)(e->dev + o_s1);
-    e->d_sums2 = (int32_t*)(e->dev + o_s2);
-    e->d_tot = (int32_t*)(e->dev + o_tot);
-    // (synchronous, once per object: the tables are the object's, a later encode on any stream reads them)
-    JE_TRY(hipMemcpy(e->d_tab, &e->tables, sizeof(Tables), hipMemcpyHostToDevice));
-    return PT_OK;
-}
-
-int grid_of(int64_t items, int per) { return (int)std::max<int64_t>(1, std::min<int64_t>((items + per - 1) / per, kMaxGrid)); }
-
-int stage(pt_jpeg_enc* e, int k, hipStream_t st) {
-    if (e->profile) JE_TRY(hipEventRecord(e->stage_ev[k], st));
+    const size_t nb = (size_t)e->geo.nblocks, worst = (size_t)e->worst;
+    uint8_t* p[7];
+    if (int rc = enc_alloc(e, {sizeof(Tables), nb * 128, nb * 4, worst + 16, (nb / kScanTile + 1) * 4, (worst / kStuffChunk + 1) * 4, 256},
+                           p, &e->tables, "tables"))
+        return rc;
+    e->d_tab = (Tables*)p[0];
+    e->d_coef = (int16_t*)p[1];
+    e->d_len = (int32_t*)p[2];
+    e->d_stream = (uint32_t*)p[3];
+    e->d_sums1 = (int32_t*)p[4];
+    e->d_sums2 = (int32_t*)p[5];
+    e->d_tot = (int32_t*)p[6];
     return PT_OK;
 }
 
@@ -648,43 +534,30 @@ int encode(pt_jpeg_enc* e, const void* src, int stride, bool acc, float samples,
     if (int rc = je_alloc(e)) return rc;
     const Geo& g = e->geo;
     const int nb = g.nblocks;
-    if (int rc = stage(e, 0, st)) return rc;
+    if (int rc = enc_stage(e, 0, st)) return rc;
     auto blocks = acc ? k_jpeg_blocks<true> : k_jpeg_blocks<false>;
     hipLaunchKernelGGL(blocks, dim3((nb + kTile - 1) / kTile), dim3(256), 0, st, src, stride, samples, g,
                        (const int32_t*)e->d_tab->q, e->d_coef);
-    if (int rc = stage(e, 1, st)) return rc;
+    if (int rc = enc_stage(e, 1, st)) return rc;
     const uint32_t* huff = e->d_tab->huff;
     hipLaunchKernelGGL(k_jpeg_count, dim3((nb + 255) / 256), dim3(256), 0, st, (const int16_t*)e->d_coef, huff, e->d_len, nb,
                        g.sub);
-    if (int rc = stage(e, 2, st)) return rc;
-    const int tiles1 = (nb + kScanTile - 1) / kScanTile, grid1 = std::min(tiles1, kMaxGrid);
-    hipLaunchKernelGGL(k_scan_reduce, dim3(grid1), dim3(256), 0, st, (const int32_t*)e->d_len, nb, e->d_sums1);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, st, e->d_sums1, tiles1, (const int32_t*)nullptr, e->d_tot);
-    hipLaunchKernelGGL(k_scan_apply, dim3(grid1), dim3(256), 0, st, e->d_len, nb, (const int32_t*)e->d_sums1);
-    if (int rc = stage(e, 3, st)) return rc;
+    if (int rc = enc_stage(e, 2, st)) return rc;
+    scan_exclusive_i32(e->d_len, nb, e->d_sums1, e->d_tot, st);
+    if (int rc = enc_stage(e, 3, st)) return rc;
     hipLaunchKernelGGL(k_jpeg_zero, dim3(grid_of(e->worst / 4 + 1, 256)), dim3(256), 0, st, e->d_stream,
                        (const int32_t*)e->d_tot);
     hipLaunchKernelGGL(k_jpeg_emit, dim3((nb + 255) / 256), dim3(256), 0, st, (const int16_t*)e->d_coef, huff,
                        (const int32_t*)e->d_len, e->d_stream, nb, g.sub);
-    if (int rc = stage(e, 4, st)) return rc;
+    if (int rc = enc_stage(e, 4, st)) return rc;
     const int grid2 = grid_of(e->worst, kStuffChunk);
     const uint8_t* stream = (const uint8_t*)e->d_stream;
-    hipLaunchKernelGGL(k_stuff_count, dim3(grid2), dim3(256), 0, st, stream, (const int32_t*)e->d_tot, e->d_sums2);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, st, e->d_sums2, 0, (const int32_t*)e->d_tot, e->d_tot + 1);
+    hipLaunchKernelGGL(k_stuff_count, dim3(grid2), dim3(256), 0, st, stream, (const int32_t*)e->d_tot, e->d_sums2, e->d_tot + 2);
+    scan_tile_sums_i32(e->d_sums2, e->d_tot + 2, e->d_tot + 1, st);
     hipLaunchKernelGGL(k_stuff_write, dim3(grid2), dim3(256), 0, st, stream, (const int32_t*)e->d_tot,
                        (const int32_t*)e->d_sums2, (const uint8_t*)e->d_tab->header, d_out, (long long)cap,
                        (long long*)d_size);
-    JE_TRY(hipGetLastError());
-    if (int rc = stage(e, 5, st)) return rc;
-    JE_TRY(hipEventRecord(e->ev, st));
-    e->ev_recorded = true;
-    return PT_OK;
-}
-
-int encode_check(const pt_jpeg_enc* e, const void* src, const uint8_t* d_out, int64_t cap, const int64_t* d_size) {
-    if (!e || !src || !d_out || !d_size) return pt::fail(PT_ERR_ARG, "null argument");
-    if (cap < 0) return pt::fail(PT_ERR_ARG, "negative output capacity");
-    return PT_OK;
+    return enc_done(e, st);
 }
 
 }  // namespace
@@ -720,13 +593,7 @@ int pt_jpeg_enc_create(int32_t width, int32_t height, const pt_jpeg_params* p, p
 }
 
 int pt_jpeg_enc_destroy(pt_jpeg_enc* e) {
-    if (!e) return PT_OK;
-    if (e->ev_recorded) (void)hipEventSynchronize(e->ev);
-    if (e->ev) (void)hipEventDestroy(e->ev);
-    for (hipEvent_t v : e->stage_ev)
-        if (v) (void)hipEventDestroy(v);
-    if (e->dev) (void)hipFree(e->dev);
-    delete e;
+    delete e;   // (~EncHead waits for the last encode)
     return PT_OK;
 }
 
@@ -754,50 +621,14 @@ int pt_jpeg_enc_accum(pt_jpeg_enc* e, const float* d_rgb, float samples, uint8_t
 
 int pt_jpeg_encode_host(int32_t width, int32_t height, const uint8_t* pix, int32_t pixel_stride, const pt_jpeg_params* p,
                         uint8_t* out, int64_t cap, int64_t* size) {
-    if (!pix || !out || !size) return pt::fail(PT_ERR_ARG, "null argument");
-    if (cap < 0) return pt::fail(PT_ERR_ARG, "negative output capacity");
-    if (pixel_stride != 3 && pixel_stride != 4) return pt::fail(PT_ERR_ARG, "the pixel stride must be 3 or 4");
-    pt_jpeg_enc* e = nullptr;
-    if (int rc = pt_jpeg_enc_create(width, height, p, &e)) return rc;
-    const size_t in_bytes = (size_t)width * height * pixel_stride;
-    const int64_t dcap = std::min(cap, pt_jpeg_enc_bound(e));
-    uint8_t* d = nullptr;   // size word | pixels | file
-    const size_t o_pix = 256, o_out = o_pix + align256(in_bytes);
-    if (hipMalloc((void**)&d, o_out + (size_t)dcap + 16) != hipSuccess) {
-        (void)hipGetLastError();
-        pt_jpeg_enc_destroy(e);
-        return pt::fail(PT_ERR_NOMEM, "hipMalloc (JPEG host encode)");
-    }
-    int64_t got = 0;
-    hipError_t he = hipMemcpy(d + o_pix, pix, in_bytes, hipMemcpyHostToDevice);
-    int rc = PT_OK;
-    if (he == hipSuccess) rc = pt_jpeg_enc_pixels(e, d + o_pix, pixel_stride, d + o_out, dcap, (int64_t*)d, nullptr);
-    if (he == hipSuccess && !rc) he = hipMemcpy(&got, d, sizeof(got), hipMemcpyDeviceToHost);   // (waits for the encode)
-    if (he == hipSuccess && !rc && got > 0) he = hipMemcpy(out, d + o_out, (size_t)got, hipMemcpyDeviceToHost);
-    pt_jpeg_enc_destroy(e);
-    (void)hipFree(d);
-    if (rc) return rc;
-    if (he != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_jpeg_encode_host: ") + hipGetErrorString(he));
-    *size = got < 0 ? -got : got;
-    if (got < 0) return pt::fail(PT_ERR_ARG, "the JPEG file needs " + std::to_string(-got) + " bytes");
-    return PT_OK;
+    return encode_host(pt_jpeg_enc_create, pt_jpeg_enc_bound, pt_jpeg_enc_pixels, width, height, pix, pixel_stride, p, out, cap, size);
 }
 
 int pt_jpeg_enc_profile(pt_jpeg_enc* e, int32_t on) {
     if (!e) return pt::fail(PT_ERR_ARG, "null JPEG encoder");
-    if (on)
-        for (hipEvent_t& v : e->stage_ev)
-            if (!v) JE_TRY(hipEventCreate(&v));
-    e->profile = on != 0;
-    return PT_OK;
+    return enc_profile(e, on);
 }
 
-int pt_jpeg_enc_profile_read(pt_jpeg_enc* e, float ms[5]) {
-    if (!e || !ms) return pt::fail(PT_ERR_ARG, "null argument");
-    if (!e->profile || !e->ev_recorded) return pt::fail(PT_ERR_ARG, "no profiled encode (pt_jpeg_enc_profile)");
-    JE_TRY(hipEventSynchronize(e->stage_ev[kStages]));
-    for (int k = 0; k < kStages; ++k) JE_TRY(hipEventElapsedTime(ms + k, e->stage_ev[k], e->stage_ev[k + 1]));
-    return PT_OK;
-}
+int pt_jpeg_enc_profile_read(pt_jpeg_enc* e, float ms[5]) { return enc_profile_read(e, ms); }
 
 }  // extern "C"

@@ -6,8 +6,8 @@
 // function of the input bytes; tests/png_enc_ref.py restates the definition and the GPU tests compare byte for
 // byte.
 //
-// Kernel shape: no inter-workgroup wait, no co-resident grid, no look-back; the prefix sum is the three-kernel
-// reduce / one-workgroup scan / apply of pt_jpeg_enc.hip (a copy: that unit is not touched).
+// Kernel shape: no inter-workgroup wait, no co-resident grid, no look-back; the prefix sum, and the host side that
+// every encoder object has, are the shared unit's (pt_enc.h).
 //   k_png_filter    rows dealt to workgroups: the five costs by workgroup reduction, the chosen row to F; the
 //                   accumulator variants fuse the conversion and re-convert the previous row
 //   k_png_block     one wave per deflate block: its chunks, staged in LDS 64 at a time by coalesced loads (a lane
@@ -16,7 +16,7 @@
 //                   (rank sort by the wave; two-queue Huffman, Kraft repair and canonical codes by one lane),
 //                   the code-length code and the header, both bit costs, the block type, the block's table
 //                   (length << 16 | reversed code) and header bits, then the bit length of every chunk
-//   k_scan_*        exclusive scan of the chunk bit lengths, in place
+//   scan            exclusive scan of the chunk bit lengths, in place (pt::scan_exclusive_i32)
 //   k_png_zero      the words of the payload up to its length ("IDAT" and the zlib header in the first two)
 //   k_png_emit      one wave per deflate block, a lane per chunk: words inside the chunk's bit range are stored,
 //                   the first and last are ORed in (atomicOr)
@@ -34,7 +34,9 @@
 
 #include <zlib.h>
 
-#include "pt_internal.h"
+#include "pt_enc.h"
+
+using namespace pt;
 
 namespace {
 
@@ -51,10 +53,8 @@ constexpr int kSyms = 286, kTab = 288; // a block's table: 286 symbols, [286] th
 constexpr int kHdrWords = 68;          // 3 + 14 + 19 * 3 + 287 * 7 = 2083 bits at most
 constexpr int kFraming = 63;           // signature 8, IHDR 25, IDAT 12, zlib header 2, Adler-32 4, IEND 12
 constexpr int kPayloadAt = 37;         // "IDAT" in the file: the stream buffer S starts with it
-constexpr int kScanPer = 4, kScanTile = 256 * kScanPer;
 constexpr int kAdlerPiece = 4096;      // bytes of F per workgroup of k_adler_part (16 per lane)
 constexpr int kCrcPiece = 256;         // bytes of the payload per lane of k_png_crc
-constexpr int kMaxGrid = 1024;
 constexpr uint32_t kAdlerMod = 65521u, kCrcPoly = 0xedb88320u;
 constexpr int kStages = 6;             // filter, block, scan, emit, checksums, out (pt_png_enc_profile)
 
@@ -64,17 +64,6 @@ struct Geo {
 };
 
 // ---- filtering ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int preview_byte(float v, float n) {   // k_preview's
-    int q = (int)((double)(v / n) * 255.0);
-    return q < 0 ? 0 : (q > 255 ? 255 : q);
-}
-__device__ __forceinline__ int save_byte(float v, float n) {      // pt_tonemap's
-    v = v / n;
-    v = v > 0.0f ? v : 0.0f;
-    v = v < 1.0f ? v : 1.0f;
-    return (int)(uint8_t)(v * 255.f);
-}
-
 // Byte i of unfiltered row y (0 left of the row and above the image).  MODE 0: pixels, 1: accumulator as
 // k_preview, 2: accumulator as pt_tonemap.
 template <int MODE>
@@ -515,74 +504,6 @@ __global__ __launch_bounds__(256) void k_png_zero(uint32_t* __restrict__ S, cons
         S[i] = i == 0 ? 0x54414449u : (i == 1 ? 0x0178u : 0u);
 }
 
-// ---- prefix sums (pt_jpeg_enc.hip's) ----------------------------------------------------------------------
-__device__ __forceinline__ int block_excl_scan(int v, int* s_w, int* total) {
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();   // (s_w may still be read by the previous call)
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    int base = 0, sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int t = s_w[k];
-        if (k < wave) base += t;
-        sum += t;
-    }
-    *total = sum;
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(256) void k_scan_reduce(const int32_t* __restrict__ in, int n, int32_t* __restrict__ sums) {
-    __shared__ int s_w[4];
-    for (int tile = (int)blockIdx.x; tile * kScanTile < n; tile += (int)gridDim.x) {
-        const int base = tile * kScanTile + (int)threadIdx.x * kScanPer;
-        int v = 0, total;
-#pragma unroll
-        for (int k = 0; k < kScanPer; ++k) v += base + k < n ? in[base + k] : 0;
-        (void)block_excl_scan(v, s_w, &total);
-        if (threadIdx.x == 0) sums[tile] = total;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_scan_sums(int32_t* __restrict__ sums, int ntiles, int32_t* __restrict__ total_out) {
-    __shared__ int s_w[4];
-    const int per = (ntiles + 255) / 256, j0 = (int)threadIdx.x * per;
-    int v = 0, total;
-    for (int j = j0; j < j0 + per && j < ntiles; ++j) v += sums[j];
-    int run = block_excl_scan(v, s_w, &total);
-    for (int j = j0; j < j0 + per && j < ntiles; ++j) {
-        const int a = sums[j];
-        sums[j] = run;
-        run += a;
-    }
-    if (threadIdx.x == 0) *total_out = total;
-}
-
-__global__ __launch_bounds__(256) void k_scan_apply(int32_t* __restrict__ io, int n, const int32_t* __restrict__ sums) {
-    __shared__ int s_w[4];
-    for (int tile = (int)blockIdx.x; tile * kScanTile < n; tile += (int)gridDim.x) {
-        const int base = tile * kScanTile + (int)threadIdx.x * kScanPer;
-        int x[kScanPer], v = 0, total;
-#pragma unroll
-        for (int k = 0; k < kScanPer; ++k) {
-            x[k] = base + k < n ? io[base + k] : 0;
-            v += x[k];
-        }
-        int run = block_excl_scan(v, s_w, &total) + sums[tile];
-#pragma unroll
-        for (int k = 0; k < kScanPer; ++k) {
-            if (base + k < n) io[base + k] = run;
-            run += x[k];
-        }
-    }
-}
-
 // ---- Adler-32 -------------------------------------------------------------------------------------------
 // s1 = 1 + sum d_i, s2 = N + sum (N - i) d_i (mod 65521).  A lane's 16 bytes [at, e): (N - e) sum + sum (e - i) d_i.
 // part[2 p], part[2 p + 1]: piece p's sum of bytes (below 2^21) and its s2 term mod 65521.
@@ -722,43 +643,22 @@ __global__ __launch_bounds__(256) void k_png_out(const uint8_t* __restrict__ S, 
     *size = end <= cap ? end : -end;
 }
 
-#define PE_TRY(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess)                                                               \
-            return pt::fail(PT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
-struct pt_png_enc {
-    int32_t W = 0, H = 0;
+struct pt_png_enc : EncHead {
+    pt_png_enc() : EncHead("PNG", "png", kStages) {}
     pt_png_params prm{};
     Geo geo{};
     int64_t stream_max = 0;           // bytes of the deflate stream at most: (9 N + 10 blocks + 7) / 8
     uint8_t head[33] = {};            // signature and IHDR
-    // The device side, one allocation made at the first encode: head | F | chunk bit lengths (then offsets) |
-    // scan tile sums | block tables | block headers | S | Adler pieces | CRC parts | total bits.
-    uint8_t* dev = nullptr;
+    // The device side: head | F | chunk bit lengths (then offsets) | scan tile sums | block tables | block
+    // headers | S | Adler pieces | CRC parts | total bits.
     uint8_t *d_head = nullptr, *d_F = nullptr;
     int32_t *d_len = nullptr, *d_sums = nullptr, *d_tot = nullptr;
     uint32_t *d_tabs = nullptr, *d_hdrs = nullptr, *d_S = nullptr, *d_adler = nullptr, *d_crc = nullptr;
-    hipEvent_t ev = nullptr;          // after the last queued work (destroy waits for it)
-    bool ev_recorded = false;
-    bool profile = false;
-    hipEvent_t stage_ev[kStages + 1] = {};
 };
 
-namespace pt {
-int png_enc_size(const pt_png_enc* e, int32_t* width, int32_t* height) {
-    if (!e) return fail(PT_ERR_ARG, "null PNG encoder");
-    *width = e->W;
-    *height = e->H;
-    return PT_OK;
-}
-}  // namespace pt
+const EncHead* pt::enc_head(const pt_png_enc* e) { return e; }
 
 namespace {
 
@@ -786,43 +686,22 @@ int size_check(int32_t W, int32_t H, int32_t block_bytes) {
 int pe_alloc(pt_png_enc* e) {
     if (e->dev) return PT_OK;
     const Geo& g = e->geo;
-    const size_t o_head = 0, o_F = 256, o_len = o_F + align256((size_t)g.N + 16), o_sums = o_len + align256((size_t)g.nchunks * 4),
-                 o_tabs = o_sums + align256(((size_t)g.nchunks / kScanTile + 1) * 4),
-                 o_hdrs = o_tabs + align256((size_t)g.nblocks * kTab * 4),
-                 o_S = o_hdrs + align256((size_t)g.nblocks * kHdrWords * 4), o_adler = o_S + align256((size_t)e->stream_max + 32),
-                 o_crc = o_adler + align256(((size_t)g.N / kAdlerPiece + 1) * 8), o_tot = o_crc + align256(kMaxGrid * 4),
-                 bytes = o_tot + 256;
-    if (hipMalloc((void**)&e->dev, bytes) != hipSuccess ||
-        (!e->ev && hipEventCreateWithFlags(&e->ev, hipEventDisableTiming) != hipSuccess)) {
-        if (e->dev) (void)hipFree(e->dev);
-        e->dev = nullptr;
-        (void)hipGetLastError();
-        return pt::fail(PT_ERR_NOMEM, "hipMalloc (PNG encoder scratch)");
-    }
-    e->d_head = e->dev + o_head;
-    e->d_F = e->dev + o_F;
-    e->d_len = (int32_t*)(e->dev + o_len);
-    e->d_sums = (int32_t*)(e->dev + o_sums);
-    e->d_tabs = (uint32_t*)(e->dev + o_tabs);
-    e->d_hdrs = (uint32_t*)(e->dev + o_hdrs);
-    e->d_S = (uint32_t*)(e->dev + o_S);
-    e->d_adler = (uint32_t*)(e->dev + o_adler);
-    e->d_crc = (uint32_t*)(e->dev + o_crc);
-    e->d_tot = (int32_t*)(e->dev + o_tot);
-    // (synchronous, once per object: the header is the object's, a later encode on any stream reads it)
-    const hipError_t he = hipMemcpy(e->d_head, e->head, sizeof(e->head), hipMemcpyHostToDevice);
-    if (he != hipSuccess) {   // (no half-made object: the next encode allocates and uploads again)
-        (void)hipFree(e->dev);
-        e->dev = nullptr;
-        return pt::fail(PT_ERR_HIP, std::string("hipMemcpy (PNG header): ") + hipGetErrorString(he));
-    }
-    return PT_OK;
-}
-
-int grid_of(int64_t items, int per) { return (int)std::max<int64_t>(1, std::min<int64_t>((items + per - 1) / per, kMaxGrid)); }
-
-int stage(pt_png_enc* e, int k, hipStream_t st) {
-    if (e->profile) PE_TRY(hipEventRecord(e->stage_ev[k], st));
+    const size_t N = (size_t)g.N, nc = (size_t)g.nchunks, nb = (size_t)g.nblocks;
+    uint8_t* p[10];
+    if (int rc = enc_alloc(e, {sizeof(e->head), N + 16, nc * 4, (nc / kScanTile + 1) * 4, nb * kTab * 4, nb * kHdrWords * 4,
+                               (size_t)e->stream_max + 32, (N / kAdlerPiece + 1) * 8, kMaxGrid * 4, 256},
+                           p, e->head, "header"))
+        return rc;
+    e->d_head = p[0];
+    e->d_F = p[1];
+    e->d_len = (int32_t*)p[2];
+    e->d_sums = (int32_t*)p[3];
+    e->d_tabs = (uint32_t*)p[4];
+    e->d_hdrs = (uint32_t*)p[5];
+    e->d_S = (uint32_t*)p[6];
+    e->d_adler = (uint32_t*)p[7];
+    e->d_crc = (uint32_t*)p[8];
+    e->d_tot = (int32_t*)p[9];
     return PT_OK;
 }
 
@@ -831,41 +710,28 @@ int encode(pt_png_enc* e, const void* src, int stride, int mode, float samples, 
            hipStream_t st) {
     if (int rc = pe_alloc(e)) return rc;
     const Geo& g = e->geo;
-    if (int rc = stage(e, 0, st)) return rc;
+    if (int rc = enc_stage(e, 0, st)) return rc;
     auto filter = mode == 0 ? k_png_filter<0> : (mode == 1 ? k_png_filter<1> : k_png_filter<2>);
     hipLaunchKernelGGL(filter, dim3(std::min(g.H, 65535)), dim3(256), 0, st, src, stride, samples, g, e->d_F);
-    if (int rc = stage(e, 1, st)) return rc;
+    if (int rc = enc_stage(e, 1, st)) return rc;
     hipLaunchKernelGGL(k_png_block, dim3(g.nblocks), dim3(64), 0, st, (const uint8_t*)e->d_F, g, e->d_tabs, e->d_hdrs, e->d_len);
-    if (int rc = stage(e, 2, st)) return rc;
-    const int tiles = (g.nchunks + kScanTile - 1) / kScanTile, grid1 = std::min(tiles, kMaxGrid);
-    hipLaunchKernelGGL(k_scan_reduce, dim3(grid1), dim3(256), 0, st, (const int32_t*)e->d_len, g.nchunks, e->d_sums);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, st, e->d_sums, tiles, e->d_tot);
-    hipLaunchKernelGGL(k_scan_apply, dim3(grid1), dim3(256), 0, st, e->d_len, g.nchunks, (const int32_t*)e->d_sums);
-    if (int rc = stage(e, 3, st)) return rc;
+    if (int rc = enc_stage(e, 2, st)) return rc;
+    scan_exclusive_i32(e->d_len, g.nchunks, e->d_sums, e->d_tot, st);
+    if (int rc = enc_stage(e, 3, st)) return rc;
     hipLaunchKernelGGL(k_png_zero, dim3(grid_of(e->stream_max / 4 + 4, 256)), dim3(256), 0, st, e->d_S, (const int32_t*)e->d_tot);
     hipLaunchKernelGGL(k_png_emit, dim3(g.nblocks), dim3(64), 0, st, (const uint8_t*)e->d_F, g, (const uint32_t*)e->d_tabs,
                        (const uint32_t*)e->d_hdrs, (const int32_t*)e->d_len, e->d_S);
-    if (int rc = stage(e, 4, st)) return rc;
+    if (int rc = enc_stage(e, 4, st)) return rc;
     hipLaunchKernelGGL(k_adler_part, dim3(grid_of(g.N, kAdlerPiece)), dim3(256), 0, st, (const uint8_t*)e->d_F, g.N, e->d_adler);
     hipLaunchKernelGGL(k_adler_fin, dim3(1), dim3(256), 0, st, (const uint32_t*)e->d_adler, g.N, (const int32_t*)e->d_tot,
                        (uint8_t*)e->d_S);
     const int crc_grid = grid_of(e->stream_max + 10, kCrcPiece * 256);
     hipLaunchKernelGGL(k_png_crc, dim3(crc_grid), dim3(256), 0, st, (const uint8_t*)e->d_S, (const int32_t*)e->d_tot, e->d_crc);
-    if (int rc = stage(e, 5, st)) return rc;
+    if (int rc = enc_stage(e, 5, st)) return rc;
     hipLaunchKernelGGL(k_png_out, dim3(grid_of(e->stream_max + 10, 256 * 16)), dim3(256), 0, st, (const uint8_t*)e->d_S,
                        (const int32_t*)e->d_tot, (const uint32_t*)e->d_crc, crc_grid, (const uint8_t*)e->d_head, d_out,
                        (long long)cap, (long long*)d_size);
-    PE_TRY(hipGetLastError());
-    if (int rc = stage(e, 6, st)) return rc;
-    PE_TRY(hipEventRecord(e->ev, st));
-    e->ev_recorded = true;
-    return PT_OK;
-}
-
-int encode_check(const pt_png_enc* e, const void* src, const uint8_t* d_out, int64_t cap, const int64_t* d_size) {
-    if (!e || !src || !d_out || !d_size) return pt::fail(PT_ERR_ARG, "null argument");
-    if (cap < 0) return pt::fail(PT_ERR_ARG, "negative output capacity");
-    return PT_OK;
+    return enc_done(e, st);
 }
 
 void put_be32(uint8_t* o, uint32_t v) { o[0] = (uint8_t)(v >> 24), o[1] = (uint8_t)(v >> 16), o[2] = (uint8_t)(v >> 8), o[3] = (uint8_t)v; }
@@ -907,13 +773,7 @@ int pt_png_enc_create(int32_t width, int32_t height, const pt_png_params* p, pt_
 }
 
 int pt_png_enc_destroy(pt_png_enc* e) {
-    if (!e) return PT_OK;
-    if (e->ev_recorded) (void)hipEventSynchronize(e->ev);
-    if (e->ev) (void)hipEventDestroy(e->ev);
-    for (hipEvent_t v : e->stage_ev)
-        if (v) (void)hipEventDestroy(v);
-    if (e->dev) (void)hipFree(e->dev);
-    delete e;
+    delete e;   // (~EncHead waits for the last encode)
     return PT_OK;
 }
 
@@ -935,50 +795,14 @@ int pt_png_enc_accum(pt_png_enc* e, const float* d_rgb, float samples, uint8_t* 
 
 int pt_png_encode_host(int32_t width, int32_t height, const uint8_t* pix, int32_t pixel_stride, const pt_png_params* p,
                        uint8_t* out, int64_t cap, int64_t* size) {
-    if (!pix || !out || !size) return pt::fail(PT_ERR_ARG, "null argument");
-    if (cap < 0) return pt::fail(PT_ERR_ARG, "negative output capacity");
-    if (pixel_stride != 3 && pixel_stride != 4) return pt::fail(PT_ERR_ARG, "the pixel stride must be 3 or 4");
-    pt_png_enc* e = nullptr;
-    if (int rc = pt_png_enc_create(width, height, p, &e)) return rc;
-    const size_t in_bytes = (size_t)width * height * pixel_stride;
-    const int64_t dcap = std::min(cap, pt_png_enc_bound(e));
-    uint8_t* d = nullptr;   // size word | pixels | file
-    const size_t o_pix = 256, o_out = o_pix + align256(in_bytes);
-    if (hipMalloc((void**)&d, o_out + (size_t)dcap + 16) != hipSuccess) {
-        (void)hipGetLastError();
-        pt_png_enc_destroy(e);
-        return pt::fail(PT_ERR_NOMEM, "hipMalloc (PNG host encode)");
-    }
-    int64_t got = 0;
-    hipError_t he = hipMemcpy(d + o_pix, pix, in_bytes, hipMemcpyHostToDevice);
-    int rc = PT_OK;
-    if (he == hipSuccess) rc = pt_png_enc_pixels(e, d + o_pix, pixel_stride, d + o_out, dcap, (int64_t*)d, nullptr);
-    if (he == hipSuccess && !rc) he = hipMemcpy(&got, d, sizeof(got), hipMemcpyDeviceToHost);   // (waits for the encode)
-    if (he == hipSuccess && !rc && got > 0) he = hipMemcpy(out, d + o_out, (size_t)got, hipMemcpyDeviceToHost);
-    pt_png_enc_destroy(e);
-    (void)hipFree(d);
-    if (rc) return rc;
-    if (he != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("pt_png_encode_host: ") + hipGetErrorString(he));
-    *size = got < 0 ? -got : got;
-    if (got < 0) return pt::fail(PT_ERR_ARG, "the PNG file needs " + std::to_string(-got) + " bytes");
-    return PT_OK;
+    return encode_host(pt_png_enc_create, pt_png_enc_bound, pt_png_enc_pixels, width, height, pix, pixel_stride, p, out, cap, size);
 }
 
 int pt_png_enc_profile(pt_png_enc* e, int32_t on) {
     if (!e) return pt::fail(PT_ERR_ARG, "null PNG encoder");
-    if (on)
-        for (hipEvent_t& v : e->stage_ev)
-            if (!v) PE_TRY(hipEventCreate(&v));
-    e->profile = on != 0;
-    return PT_OK;
+    return enc_profile(e, on);
 }
 
-int pt_png_enc_profile_read(pt_png_enc* e, float ms[6]) {
-    if (!e || !ms) return pt::fail(PT_ERR_ARG, "null argument");
-    if (!e->profile || !e->ev_recorded) return pt::fail(PT_ERR_ARG, "no profiled encode (pt_png_enc_profile)");
-    PE_TRY(hipEventSynchronize(e->stage_ev[kStages]));
-    for (int k = 0; k < kStages; ++k) PE_TRY(hipEventElapsedTime(ms + k, e->stage_ev[k], e->stage_ev[k + 1]));
-    return PT_OK;
-}
+int pt_png_enc_profile_read(pt_png_enc* e, float ms[6]) { return enc_profile_read(e, ms); }
 
 }  // extern "C"

@@ -421,21 +421,20 @@ class PathTracer:
     def preview_rgba(self, iteration: int, dst_ptr: int, stream=None) -> None:
         check_pt(lib().pt_preview_rgba(self._h, int(iteration), C.c_void_p(dst_ptr), _stream_ptr(stream)))
 
+    def _preview_file(self, entry, iteration: int, encoder: "_Encoder", stream) -> bytes:
+        out, size = encoder._buffers()
+        check_pt(entry(self._h, int(iteration), encoder._h, out.data_ptr(), encoder.cap, size.data_ptr(), _stream_ptr(stream)))
+        return encoder._read(stream)
+
     def preview_jpeg(self, iteration: int, encoder: "JpegEncoder", stream=None) -> bytes:
         """The accumulated image of `iteration` iterations as preview_rgba converts it, as a JPEG file
         encoded on the device by `encoder` (pt_preview_jpeg): only the file crosses to the host."""
-        out, size = encoder._buffers()
-        check_pt(lib().pt_preview_jpeg(self._h, int(iteration), encoder._h, out.data_ptr(), encoder.cap, size.data_ptr(),
-                                       _stream_ptr(stream)))
-        return encoder._read(stream)
+        return self._preview_file(lib().pt_preview_jpeg, iteration, encoder, stream)
 
     def preview_png(self, iteration: int, encoder: "PngEncoder", stream=None) -> bytes:
         """The accumulated image of `iteration` iterations as a PNG file written on the device by `encoder`
         (pt_preview_png), converted as the encoder's params.conv says: only the file crosses to the host."""
-        out, size = encoder._buffers()
-        check_pt(lib().pt_preview_png(self._h, int(iteration), encoder._h, out.data_ptr(), encoder.cap, size.data_ptr(),
-                                      _stream_ptr(stream)))
-        return encoder._read(stream)
+        return self._preview_file(lib().pt_preview_png, iteration, encoder, stream)
 
     def save_png(self, path: str, iteration: int) -> str:
         """saveImage's file written on the device: save_image's pixels (pt_tonemap's conversion, x-mirrored) of the
@@ -716,25 +715,24 @@ def _jpeg_params(quality: int, subsampling, mirror_x: bool) -> "N.JpegParams":
     return p
 
 
-class JpegEncoder:
-    """pt_jpeg_enc: a baseline JPEG encoder on the device for (height, width) images.
-    It owns its scratch and a device output buffer of `cap` bytes (default: `bound`, which every file
-    fits); params: a JpegParams (default: quality 90, 4:2:0)."""
+class _Encoder:
+    """What the device encoders share: an object for (height, width) images that owns its scratch and a device
+    output buffer of `cap` bytes (default: `bound`, which every file fits).  A subclass names its format, its
+    parameter type and, in _entry(library), its create, bound, destroy, pixels and accum entry points."""
 
-    _kind = "jpeg"   # the entry points are pt_<kind>_enc_*
-
-    def __init__(self, width: int, height: int, params: "N.JpegParams | None" = None, cap: int | None = None):
+    def __init__(self, width: int, height: int, params=None, cap: int | None = None):
         self.width, self.height = int(width), int(height)
         self._h = C.c_void_p()
-        prm = params if params is not None else N.JpegParams.default()
-        check_pt(lib().pt_jpeg_enc_create(self.width, self.height, C.byref(prm), C.byref(self._h)))
-        self.bound = int(lib().pt_jpeg_enc_bound(self._h))
-        self.cap = self.bound if cap is None else int(cap)
         self._out = self._size = None
+        create, bound, self._destroy, self._pixels, self._accum = self._entry(lib())
+        prm = params if params is not None else self._params.default()
+        check_pt(create(self.width, self.height, C.byref(prm), C.byref(self._h)))
+        self.bound = int(bound(self._h))
+        self.cap = self.bound if cap is None else int(cap)
 
     def free(self) -> None:
         if self._h is not None and self._h.value:
-            check_pt(getattr(lib(), f"pt_{self._kind}_enc_destroy")(self._h))
+            check_pt(self._destroy(self._h))
         self._h = None
         self._out = self._size = None
 
@@ -743,13 +741,6 @@ class JpegEncoder:
             self.free()
         except Exception:
             pass
-
-    def header(self) -> bytes:
-        """The file header SOI .. SOS (pt_jpeg_enc_header; no device needed)."""
-        n = int(lib().pt_jpeg_enc_header(self._h, None, 0))
-        buf = (C.c_uint8 * n)()
-        lib().pt_jpeg_enc_header(self._h, buf, n)
-        return bytes(buf)
 
     def _buffers(self):
         import torch
@@ -765,7 +756,7 @@ class JpegEncoder:
             (stream if hasattr(stream, "synchronize") else torch.cuda.ExternalStream(int(stream))).synchronize()
         size = int(self._size.cpu()[0])
         if size < 0:
-            raise N.PtError(1, f"the {self._kind.upper()} file needs {-size} bytes, the output buffer holds {self.cap}")
+            raise N.PtError(1, f"the {self._format} file needs {-size} bytes, the output buffer holds {self.cap}")
         return self._out[:size].cpu().numpy().tobytes()
 
     def encode(self, src, pixel_stride: int | None = None, samples: float | None = None, stream=None) -> bytes:
@@ -790,49 +781,62 @@ class JpegEncoder:
             ptr, pixel_stride = keep.data_ptr(), int(t.shape[2])
         out, size = self._buffers()
         if samples is not None:
-            check_pt(getattr(lib(), f"pt_{self._kind}_enc_accum")(self._h, C.c_void_p(ptr), float(samples), out.data_ptr(),
-                                                                  self.cap, size.data_ptr(), _stream_ptr(stream)))
+            check_pt(self._accum(self._h, C.c_void_p(ptr), float(samples), out.data_ptr(), self.cap, size.data_ptr(),
+                                 _stream_ptr(stream)))
         else:
-            check_pt(getattr(lib(), f"pt_{self._kind}_enc_pixels")(self._h, C.c_void_p(ptr), int(pixel_stride), out.data_ptr(),
-                                                                   self.cap, size.data_ptr(), _stream_ptr(stream)))
+            check_pt(self._pixels(self._h, C.c_void_p(ptr), int(pixel_stride), out.data_ptr(), self.cap, size.data_ptr(),
+                                  _stream_ptr(stream)))
         data = self._read(stream)
         del keep
         return data
 
 
-def encode_jpeg(rgb8: np.ndarray, quality: int = 90, subsampling="420", mirror_x: bool = False) -> bytes:
-    """An (H, W, 3 | 4) uint8 image as a baseline JPEG file, encoded on the device (pt_jpeg_encode_host)."""
+class JpegEncoder(_Encoder):
+    """pt_jpeg_enc: a baseline JPEG encoder on the device; params: a JpegParams (default: quality
+    90, 4:2:0)."""
+
+    _format, _params = "JPEG", N.JpegParams
+
+    _entry = staticmethod(lambda L: (L.pt_jpeg_enc_create, L.pt_jpeg_enc_bound, L.pt_jpeg_enc_destroy, L.pt_jpeg_enc_pixels,
+                                     L.pt_jpeg_enc_accum))
+
+    def header(self) -> bytes:
+        """The file header SOI .. SOS (pt_jpeg_enc_header; no device needed)."""
+        n = int(lib().pt_jpeg_enc_header(self._h, None, 0))
+        buf = (C.c_uint8 * n)()
+        lib().pt_jpeg_enc_header(self._h, buf, n)
+        return bytes(buf)
+
+
+class PngEncoder(_Encoder):
+    """pt_png_enc: a PNG encoder on the device; params: a PngParams (default: adaptive filter,
+    32 KiB deflate blocks)."""
+
+    _format, _params = "PNG", N.PngParams
+
+    _entry = staticmethod(lambda L: (L.pt_png_enc_create, L.pt_png_enc_bound, L.pt_png_enc_destroy, L.pt_png_enc_pixels,
+                                     L.pt_png_enc_accum))
+
+
+def _encode_host(entry, rgb8: np.ndarray, prm, bound) -> bytes:
+    """encode_jpeg and encode_png: bound(w, h) is the encoder's bound, restated."""
     img = np.ascontiguousarray(rgb8, dtype=np.uint8)
     if img.ndim != 3 or img.shape[2] not in (3, 4):
         raise ValueError(f"image shape {img.shape}: expected (H, W, 3 | 4)")
     h, w = img.shape[:2]
-    prm = _jpeg_params(quality, subsampling, mirror_x)
-    m = 8 if prm.subsampling == N.JPEG_444 else 16
-    blocks = (3 if m == 8 else 6) * ((w + m - 1) // m) * ((h + m - 1) // m)
-    out = np.empty(623 + 2 * (blocks * 208) + 2, np.uint8)   # pt_jpeg_enc_bound
+    out = np.empty(bound(w, h), np.uint8)
     n = C.c_int64(0)
-    check_pt(lib().pt_jpeg_encode_host(w, h, img.ctypes.data, img.shape[2], C.byref(prm), out.ctypes.data, out.size,
-                                       C.byref(n)))
+    check_pt(entry(w, h, img.ctypes.data, img.shape[2], C.byref(prm), out.ctypes.data, out.size, C.byref(n)))
     return out[:n.value].tobytes()
 
 
-class PngEncoder(JpegEncoder):
-    """pt_png_enc: a PNG encoder on the device for (height, width) images, with JpegEncoder's
-    encode(), bound, cap and free(); params: a PngParams (default: adaptive filter, 32 KiB deflate blocks)."""
-
-    _kind = "png"
-
-    def __init__(self, width: int, height: int, params: "N.PngParams | None" = None, cap: int | None = None):
-        self.width, self.height = int(width), int(height)
-        self._h = C.c_void_p()
-        self._out = self._size = None
-        prm = params if params is not None else N.PngParams.default()
-        check_pt(lib().pt_png_enc_create(self.width, self.height, C.byref(prm), C.byref(self._h)))
-        self.bound = int(lib().pt_png_enc_bound(self._h))
-        self.cap = self.bound if cap is None else int(cap)
-
-    def header(self) -> bytes:
-        raise NotImplementedError("a PNG file has no fixed header beyond the signature and IHDR")
+def encode_jpeg(rgb8: np.ndarray, quality: int = 90, subsampling="420", mirror_x: bool = False) -> bytes:
+    """An (H, W, 3 | 4) uint8 image as a baseline JPEG file, encoded on the device (pt_jpeg_encode_host)."""
+    prm = _jpeg_params(quality, subsampling, mirror_x)
+    m = 8 if prm.subsampling == N.JPEG_444 else 16
+    per = 3 if m == 8 else 6   # blocks of an MCU; pt_jpeg_enc_bound: 208 bytes a block, twice when stuffed
+    return _encode_host(lib().pt_jpeg_encode_host, rgb8, prm,
+                        lambda w, h: 623 + 2 * (per * ((w + m - 1) // m) * ((h + m - 1) // m) * 208) + 2)
 
 
 def _png_params(filter=None, block_bytes: int | None = None, conv: int | None = None, mirror_x: bool = False) -> "N.PngParams":
@@ -849,17 +853,12 @@ def _png_params(filter=None, block_bytes: int | None = None, conv: int | None = 
 
 def encode_png(rgb8: np.ndarray, filter=None, block_bytes: int | None = None, mirror_x: bool = False) -> bytes:
     """An (H, W, 3 | 4) uint8 image as an 8-bit RGB PNG file, written on the device (pt_png_encode_host)."""
-    img = np.ascontiguousarray(rgb8, dtype=np.uint8)
-    if img.ndim != 3 or img.shape[2] not in (3, 4):
-        raise ValueError(f"image shape {img.shape}: expected (H, W, 3 | 4)")
-    h, w = img.shape[:2]
     prm = _png_params(filter, block_bytes, None, mirror_x)
-    n_f = h * (1 + 3 * w)
-    out = np.empty((9 * n_f + 10 * -(-n_f // max(prm.block_bytes, 1)) + 7) // 8 + 63, np.uint8)   # pt_png_enc_bound
-    n = C.c_int64(0)
-    check_pt(lib().pt_png_encode_host(w, h, img.ctypes.data, img.shape[2], C.byref(prm), out.ctypes.data, out.size,
-                                      C.byref(n)))
-    return out[:n.value].tobytes()
+
+    def bound(w, h):   # pt_png_enc_bound
+        n_f = h * (1 + 3 * w)
+        return (9 * n_f + 10 * -(-n_f // max(prm.block_bytes, 1)) + 7) // 8 + 63
+    return _encode_host(lib().pt_png_encode_host, rgb8, prm, bound)
 
 
 def tonemap(image: np.ndarray, samples: float) -> np.ndarray:

@@ -76,6 +76,16 @@ def test_random_bytes_quality_100(gpu_device, sub):
     assert _gpu(img, 100, sub) == ref.data
 
 
+def test_stuffing_scan_two_sums_per_lane(gpu_device):
+    """512 x 512 random bytes, quality 100, 4:4:4: more than 256 stuffing chunks, so the one-workgroup scan of
+    their sums takes two per lane, and the last chunk is partial."""
+    img = np.random.default_rng(11).integers(0, 256, (512, 512, 3), dtype=np.uint8)
+    ref = R.encode(img, 100, R.S444)
+    assert len(ref.coefs) == 12288 and ref.unstuffed_bytes == 1069358
+    assert ref.unstuffed_bytes > 256 * R.STUFF_CHUNK and ref.unstuffed_bytes % R.STUFF_CHUNK != 0
+    assert _gpu(img, 100, R.S444) == ref.data
+
+
 def test_zero_runs_of_16(gpu_device):
     """One block of the highest-frequency cosine on a flat field: a run of 62 zeros before the last coefficient."""
     x = np.arange(8)
@@ -184,6 +194,25 @@ def test_reuse_one_object(gpu_device):
     finally:
         enc.free()
     assert got == [R.encode(im, 100, R.S444).data for im in (rnd, flat, other, rnd)]
+
+
+def test_two_encoders_alive(gpu_device):
+    """A JPEG and a PNG encoder used alternately on one stream: nothing of one object's encode reaches the other's
+    (the unit the two share keeps no state of its own)."""
+    import torch
+    from cuda_pathtracer_amd import JpegEncoder, PngEncoder
+    from tests import png_enc_ref as RP
+    a, b = _noisy(64, 48), _noisy(64, 48, seed=1)
+    assert not np.array_equal(a, b)
+    jpg, png, st = JpegEncoder(64, 48), PngEncoder(64, 48), torch.cuda.Stream()
+    try:
+        got = [enc.encode(im, stream=st) for enc, im in ((jpg, a), (png, a), (jpg, b), (png, b), (jpg, a))]
+    finally:
+        jpg.free()
+        png.free()
+    ja, jb = R.encode(a, 90, R.S420).data, R.encode(b, 90, R.S420).data
+    assert got == [ja, RP.encode(a).data, jb, RP.encode(b).data, ja]
+    assert got[0] == got[4] != got[2]
 
 
 def test_non_default_stream_behind_a_pass(cornell_path, gpu_device):
