@@ -152,6 +152,20 @@ class PngParams(C.Structure):
 PNG_FILTER_ADAPTIVE = 5                  # PT_PNG_FILTER_ADAPTIVE
 PNG_CONV_PREVIEW, PNG_CONV_SAVE = 0, 1   # PT_PNG_CONV_*
 assert C.sizeof(PngParams) == 32
+
+
+class HdrParams(C.Structure):
+    """pt_hdr_params; HdrParams.default() = pt_hdr_params_default (no mirror)."""
+    _fields_ = [("mirror_x", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+    @classmethod
+    def default(cls) -> "HdrParams":
+        p = cls()
+        lib().pt_hdr_params_default(C.byref(p))
+        return p
+
+
+assert C.sizeof(HdrParams) == 32
 assert C.sizeof(DenoiseParams) == 32 and C.sizeof(DenoiseVarParams) == 32 and C.sizeof(TemporalParams) == 32
 assert C.sizeof(AdaptiveParams) == 32
 assert C.sizeof(Geom) == 272 and C.sizeof(Material) == 48 and C.sizeof(Triangle) == 124
@@ -324,6 +338,15 @@ SIGNATURES = {
     "pt_preview_png": (_I, [_P, _I, _P, _P, C.c_int64, _P, _P]),
     "pt_png_enc_profile": (_I, [_P, _I]),
     "pt_png_enc_profile_read": (_I, [_P, _FP]),
+    "pt_hdr_params_default": (None, [C.POINTER(HdrParams)]),
+    "pt_hdr_enc_create": (_I, [_I, _I, C.POINTER(HdrParams), C.POINTER(_P)]),
+    "pt_hdr_enc_destroy": (_I, [_P]),
+    "pt_hdr_enc_bound": (C.c_int64, [_P]),
+    "pt_hdr_enc_accum": (_I, [_P, _P, _F, _P, C.c_int64, _P, _P]),
+    "pt_hdr_encode_host": (_I, [_I, _I, _P, _F, C.POINTER(HdrParams), _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "pt_preview_hdr": (_I, [_P, _I, _P, _P, C.c_int64, _P, _P]),
+    "pt_hdr_enc_profile": (_I, [_P, _I]),
+    "pt_hdr_enc_profile_read": (_I, [_P, _FP]),
 }
 
 _lib = None
@@ -346,7 +369,8 @@ def _preload_torch() -> None:
 # pt_ctx_depart_counts: the A/B against the build before the room's departure claim;
 # pt_ctx_exact_counts, pt_selftest_exact: the A/B against the build before the exact tests' single gate;
 # pt_jpeg_*, pt_preview_jpeg: the A/B against the build before the JPEG encoder; pt_png_*, pt_preview_png: the
-# A/B against the build before the PNG encoder).
+# A/B against the build before the PNG encoder; pt_hdr_*, pt_preview_hdr: the A/B against the build before the
+# HDR encoder).
 _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
              "pt_ctx_exact_counts", "pt_selftest_exact",
              "pt_moments_create",
@@ -365,7 +389,9 @@ _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "p
              "pt_jpeg_enc_pixels", "pt_jpeg_enc_accum", "pt_jpeg_encode_host", "pt_preview_jpeg", "pt_jpeg_enc_profile",
              "pt_jpeg_enc_profile_read",
              "pt_png_params_default", "pt_png_enc_create", "pt_png_enc_destroy", "pt_png_enc_bound", "pt_png_enc_pixels",
-             "pt_png_enc_accum", "pt_png_encode_host", "pt_preview_png", "pt_png_enc_profile", "pt_png_enc_profile_read"}
+             "pt_png_enc_accum", "pt_png_encode_host", "pt_preview_png", "pt_png_enc_profile", "pt_png_enc_profile_read",
+             "pt_hdr_params_default", "pt_hdr_enc_create", "pt_hdr_enc_destroy", "pt_hdr_enc_bound", "pt_hdr_enc_accum",
+             "pt_hdr_encode_host", "pt_preview_hdr", "pt_hdr_enc_profile", "pt_hdr_enc_profile_read"}
 
 
 def lib() -> C.CDLL:

@@ -426,4 +426,11 @@ int pt_preview_png(pt_ctx* ctx, int32_t iter, pt_png_enc* e, uint8_t* d_out, int
                         d_size, stream);
 }
 
+// ---- final images as Radiance HDR ---------------------------------------------
+// The same ordering; the encoder's convert kernel divides the accumulator by iter.
+int pt_preview_hdr(pt_ctx* ctx, int32_t iter, pt_hdr_enc* e, uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream) {
+    return preview_file(ctx, iter, e, pt_hdr_enc_accum, "HDR", "pt_preview_hdr needs the whole image (world == 1)", d_out, cap,
+                        d_size, stream);
+}
+
 }  // extern "C"

@@ -69,10 +69,11 @@ int adaptive_update_check(const pt_adaptive* a, float batch_samples);
 int temporal_case(const pt_temporal* t, const pt_camera* cam, float samples);
 int temporal_staging(pt_temporal* t, int kind, float** gA, float** gB, float** alb);
 int temporal_size(const pt_temporal* t, int32_t* width, int32_t* height);
-// The device encoders (pt_enc.h): what both objects begin with, and the image size one was created for (e not null)
+// The device encoders (pt_enc.h): what every object begins with, and the image size one was created for (e not null)
 struct EncHead;
 const EncHead* enc_head(const pt_jpeg_enc* e);
 const EncHead* enc_head(const pt_png_enc* e);
+const EncHead* enc_head(const pt_hdr_enc* e);
 void enc_size(const EncHead* e, int32_t* width, int32_t* height);
 
 inline float bits_to_float(int32_t v) {

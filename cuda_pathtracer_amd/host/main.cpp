@@ -5,6 +5,9 @@
 //
 //   pathtracer_amd SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise]
 //                  [--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png]
+//                  [--device-hdr]
+// --device-hdr, with --hdr, writes the main .hdr file on the device (pt_preview_hdr: the same name and the same
+// bytes; the denoised and adaptive .hdr files stay on the host writer).
 // --device-png writes the final PNG on the device (pt_preview_png with pt_tonemap's conversion and the x
 // mirror: the same name and the same pixels, another file; only the file crosses to the host).
 // --denoise also writes the a-trous-filtered image (pt_denoise_image) as ...samp.denoised.png (and
@@ -61,33 +64,65 @@ std::string saveImage(const Scene& scene, const std::string& dir, const std::str
     return filename;
 }
 
-// --device-png: saveImage's file name and pixels, the file written by the device encoder.
-std::string saveImageDevice(const Scene& scene, const std::string& dir, const std::string& start, int iteration) {
+// --device-png, --device-hdr: saveImage's file name, the file written by a device encoder.  encode(d_out, cap,
+// d_size) queues it; the size word, then that many bytes, cross to the host.
+template <class Encode>
+std::string saveDeviceFile(const Scene& scene, const std::string& dir, const std::string& start, int iteration, const char* ext,
+                           int64_t cap, Encode encode) {
     std::ostringstream ss;
     ss << scene.state.imageName << "." << start << "." << (float)iteration << "samp";
-    std::string filename = (dir.empty() ? std::string() : dir + "/") + ss.str() + ".png";
+    std::string filename = (dir.empty() ? std::string() : dir + "/") + ss.str() + ext;
     auto die = [](const char* what, const char* why) {
         std::fprintf(stderr, "saveImage (device): %s: %s\n", what, why);
         std::exit(EXIT_FAILURE);
     };
-    pt_png_params prm;
-    pt_png_params_default(&prm);
-    prm.conv = PT_PNG_CONV_SAVE;
-    prm.mirror_x = 1;
-    pt_png_enc* enc = nullptr;
-    if (pt_png_enc_create(scene.state.camera.res[0], scene.state.camera.res[1], &prm, &enc)) die("encoder", pt_last_error());
-    const int64_t cap = pt_png_enc_bound(enc);
     uint8_t* d = nullptr;   // size word | file
     if (hipMalloc((void**)&d, 256 + (size_t)cap) != hipSuccess) die("hipMalloc", "out of device memory");
-    if (pt_preview_png(pathtraceContext(), iteration, enc, d + 256, cap, (int64_t*)d, nullptr)) die("encode", pt_last_error());
+    if (encode(d + 256, cap, (int64_t*)d)) die("encode", pt_last_error());
     int64_t size = 0;
     if (hipMemcpy(&size, d, sizeof(size), hipMemcpyDeviceToHost) != hipSuccess || size <= 0) die("size", "copy failed");
     std::vector<uint8_t> file((size_t)size);
     if (hipMemcpy(file.data(), d + 256, (size_t)size, hipMemcpyDeviceToHost) != hipSuccess) die("file", "copy failed");
     (void)hipFree(d);
-    pt_png_enc_destroy(enc);
     FILE* f = std::fopen(filename.c_str(), "wb");
     if (!f || std::fwrite(file.data(), 1, file.size(), f) != file.size() || std::fclose(f)) die("write", filename.c_str());
+    return filename;
+}
+
+// --device-png: saveImage's pixels (pt_tonemap's conversion, x-mirrored).
+std::string saveImageDevice(const Scene& scene, const std::string& dir, const std::string& start, int iteration) {
+    pt_png_params prm;
+    pt_png_params_default(&prm);
+    prm.conv = PT_PNG_CONV_SAVE;
+    prm.mirror_x = 1;
+    pt_png_enc* enc = nullptr;
+    if (pt_png_enc_create(scene.state.camera.res[0], scene.state.camera.res[1], &prm, &enc)) {
+        std::fprintf(stderr, "saveImage (device): encoder: %s\n", pt_last_error());
+        std::exit(EXIT_FAILURE);
+    }
+    const std::string filename = saveDeviceFile(scene, dir, start, iteration, ".png", pt_png_enc_bound(enc),
+                                                [&](uint8_t* d_out, int64_t cap, int64_t* d_size) {
+        return pt_preview_png(pathtraceContext(), iteration, enc, d_out, cap, d_size, nullptr);
+    });
+    pt_png_enc_destroy(enc);
+    return filename;
+}
+
+// --device-hdr: pt_save_hdr's bytes (x-mirrored, accumulator / iteration).
+std::string saveHdrDevice(const Scene& scene, const std::string& dir, const std::string& start, int iteration) {
+    pt_hdr_params prm;
+    pt_hdr_params_default(&prm);
+    prm.mirror_x = 1;
+    pt_hdr_enc* enc = nullptr;
+    if (pt_hdr_enc_create(scene.state.camera.res[0], scene.state.camera.res[1], &prm, &enc)) {
+        std::fprintf(stderr, "saveImage (device): encoder: %s\n", pt_last_error());
+        std::exit(EXIT_FAILURE);
+    }
+    const std::string filename = saveDeviceFile(scene, dir, start, iteration, ".hdr", pt_hdr_enc_bound(enc),
+                                                [&](uint8_t* d_out, int64_t cap, int64_t* d_size) {
+        return pt_preview_hdr(pathtraceContext(), iteration, enc, d_out, cap, d_size, nullptr);
+    });
+    pt_hdr_enc_destroy(enc);
     return filename;
 }
 
@@ -196,14 +231,14 @@ int main(int argc, char** argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2) {
         std::printf("Usage: %s SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise] "
-                    "[--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png]\n", argv[0]);
+                    "[--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png] [--device-hdr]\n", argv[0]);
         return 1;
     }
     const char* sceneFile = argv[1];
     int iterations = -1;
     std::string out_dir, aov_dir;
     bool sort = false, png = true, hdr = false, denoise = false, denoise_var = false, aov = false, adaptive = false;
-    bool device_png = false;
+    bool device_png = false, device_hdr = false;
     float adaptive_threshold = 0.0f;
     int adaptive_every = 4;
     for (int i = 2; i < argc; ++i) {
@@ -212,6 +247,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--sort")) sort = true;
         else if (!std::strcmp(argv[i], "--no-png")) png = false;
         else if (!std::strcmp(argv[i], "--device-png")) device_png = true;
+        else if (!std::strcmp(argv[i], "--device-hdr")) device_hdr = true;
         else if (!std::strcmp(argv[i], "--hdr")) hdr = true;   // also write the saveHDR .hdr file
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
         else if (!std::strcmp(argv[i], "--denoise-variance")) denoise_var = true;
@@ -255,7 +291,9 @@ int main(int argc, char** argv) {
     if (png)
         std::printf("wrote %s\n", device_png ? saveImageDevice(*scene, out_dir, startTimeString, iteration).c_str()
                                              : saveImage(*scene, out_dir, startTimeString, iteration).c_str());
-    if (hdr) std::printf("wrote %s\n", saveImage(*scene, out_dir, startTimeString, iteration, true).c_str());
+    if (hdr)
+        std::printf("wrote %s\n", device_hdr ? saveHdrDevice(*scene, out_dir, startTimeString, iteration).c_str()
+                                             : saveImage(*scene, out_dir, startTimeString, iteration, true).c_str());
     if (denoise) {
         std::vector<float> dn((size_t)scene->state.camera.res[0] * scene->state.camera.res[1] * 3);
         pt_denoise_params prm;

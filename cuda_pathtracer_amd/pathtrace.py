@@ -20,8 +20,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, JpegParams, PngParams, TemporalParams, check_pt,  # noqa: F401
-                      lib)
+from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, HdrParams, JpegParams, PngParams, TemporalParams,  # noqa: F401
+                      check_pt, lib)
 
 SPHERE, CUBE, MESH = 0, 1, 2
 
@@ -450,6 +450,25 @@ class PathTracer:
             f.write(data)
         return str(path)
 
+    def preview_hdr(self, iteration: int, encoder: "HdrEncoder", stream=None) -> bytes:
+        """The accumulated image of `iteration` iterations as a Radiance HDR file written on the device by
+        `encoder` (pt_preview_hdr): only the file crosses to the host."""
+        return self._preview_file(lib().pt_preview_hdr, iteration, encoder, stream)
+
+    def save_hdr(self, path: str, iteration: int) -> str:
+        """save_image_hdr's file (x-mirrored, accumulator / iteration) written on the device, without the
+        accumulator crossing to the host."""
+        prm = N.HdrParams.default()
+        prm.mirror_x = 1
+        enc = HdrEncoder(self.width, self.rows, prm)
+        try:
+            data = self.preview_hdr(iteration, enc)
+        finally:
+            enc.free()
+        with open(path, "wb") as f:
+            f.write(data)
+        return str(path)
+
     def gbuffer(self) -> dict:
         """First-hit feature planes of the tile (pt_get_gbuffer; the deterministic camera ray): normal
         (rows, W, 3), mat (rows, W) int32 with -1 on a miss, position (rows, W, 3), t (rows, W) with -1
@@ -818,6 +837,20 @@ class PngEncoder(_Encoder):
                                      L.pt_png_enc_accum))
 
 
+class HdrEncoder(_Encoder):
+    """pt_hdr_enc: a Radiance HDR encoder on the device; params: an HdrParams (default: no
+    mirror).  Its source is always a float accumulator."""
+
+    _format, _params = "HDR", N.HdrParams
+
+    _entry = staticmethod(lambda L: (L.pt_hdr_enc_create, L.pt_hdr_enc_bound, L.pt_hdr_enc_destroy, None, L.pt_hdr_enc_accum))
+
+    def encode(self, src, samples: float, stream=None) -> bytes:
+        """One file.  src: an (H, W, 3) float32 array or tensor of `samples` samples, or a device pointer (int)
+        to one."""
+        return super().encode(src, samples=float(samples), stream=stream)
+
+
 def _encode_host(entry, rgb8: np.ndarray, prm, bound) -> bytes:
     """encode_jpeg and encode_png: bound(w, h) is the encoder's bound, restated."""
     img = np.ascontiguousarray(rgb8, dtype=np.uint8)
@@ -885,6 +918,22 @@ def encode_hdr(image: np.ndarray, samples: float) -> bytes:
     check_pt(lib().pt_encode_hdr(img.ctypes.data, img.shape[1], img.shape[0], float(samples), buf, n.value,
                                  C.byref(n)))
     return bytes(buf)
+
+
+def encode_hdr_device(image: np.ndarray, samples: float, mirror_x: bool = True) -> bytes:
+    """encode_hdr's file written on the device (pt_hdr_encode_host); mirror_x=False keeps the array's columns."""
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"image shape {img.shape}: expected (H, W, 3)")
+    h, w = img.shape[:2]
+    prm = N.HdrParams.default()
+    prm.mirror_x = int(bool(mirror_x))
+    flat = w < 8 or w >= 32768   # pt_hdr_enc_bound, with room for the header
+    out = np.empty(160 + (4 * w * h if flat else h * (4 + 4 * (w + (w + 127) // 128))), np.uint8)
+    n = C.c_int64(0)
+    check_pt(lib().pt_hdr_encode_host(w, h, img.ctypes.data, float(samples), C.byref(prm), out.ctypes.data, out.size,
+                                      C.byref(n)))
+    return out[:n.value].tobytes()
 
 
 def save_image_hdr(path: str, image: np.ndarray, samples: float) -> str:

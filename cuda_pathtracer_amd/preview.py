@@ -16,7 +16,8 @@ render process:
                    DESIGN.md §14): GET /frame.jpg, and GET /stream.mjpg, which pushes each new
                    iteration's file once (multipart/x-mixed-replace).  With --png-device
                    /frame.png is written on the device too (pt_preview_png): the
-                   same pixels, another file.
+                   same pixels, another file.  GET /frame.hdr is the current accumulation as a
+                   Radiance HDR file, always written on the device (pt_preview_hdr).
 
     python -m cuda_pathtracer_amd.preview SCENE.json [--port 8080]   (then open the printed URL)
 
@@ -38,8 +39,8 @@ from pathlib import Path
 
 import numpy as np
 
-from .pathtrace import (DenoiseVarParams, GuiDataContainer, JpegEncoder, PathTracer, PngEncoder, Scene, TemporalHistory,
-                        _jpeg_params, _png_params, encode_jpeg, encode_png, save_image, tonemap)
+from .pathtrace import (DenoiseVarParams, GuiDataContainer, HdrEncoder, HdrParams, JpegEncoder, PathTracer, PngEncoder, Scene,
+                        TemporalHistory, _jpeg_params, _png_params, encode_jpeg, encode_png, save_image, tonemap)
 
 F32 = np.float32
 PI = F32(3.1415926535897932384626422832795028841971)   # utilities.h PI (a float)
@@ -128,6 +129,7 @@ class PreviewSession:
         self._enc = None
         self.png_device = bool(png_device)
         self._png_enc = None
+        self._hdr_enc = None         # /frame.hdr's encoder, made at the first request
         self._raw_frame = False      # the current frame is the context's accumulator as pt_preview_rgba converts it
         self.jpeg_bytes = b""        # the current frame's file (JPEG mode)
         self.frame_serial = 0        # counts the files: /stream.mjpg sends each once
@@ -289,6 +291,19 @@ class PreviewSession:
             self._current_rgba()
             return encode_png(self.rgba, mirror_x=True)
 
+    def hdr_frame(self) -> bytes | None:
+        """/frame.hdr: the current accumulation (accumulator / iteration, x-mirrored like every saved image) as a
+        Radiance HDR file, always written on the device (pt_preview_hdr); None when there is nothing to encode
+        (no iteration yet, or the session is finished and its context freed)."""
+        with self.lock:
+            if self.ctx is None or self.iteration <= 0:
+                return None
+            if self._hdr_enc is None:
+                prm = HdrParams.default()
+                prm.mirror_x = 1
+                self._hdr_enc = HdrEncoder(self.width, self.height, prm)
+            return self.ctx.preview_hdr(self.iteration, self._hdr_enc)
+
     def _current_rgba(self) -> None:
         """JPEG mode and png_device: the PBO of the current frame, read when something asks for it."""
         if not self._rgba_current and self.ctx is not None:
@@ -363,6 +378,9 @@ class PreviewSession:
             if self._png_enc is not None:
                 self._png_enc.free()
                 self._png_enc = None
+            if self._hdr_enc is not None:
+                self._hdr_enc.free()
+                self._hdr_enc = None
             self.frame_ready.notify_all()
 
     # ---- what the window shows ----------------------------------------------------------------
@@ -511,6 +529,12 @@ class PreviewServer:
                     self._send(200, srv.frame_jpeg()[1], "image/jpeg")
                 elif path == "/stream.mjpg" and jpeg:
                     self._stream()
+                elif path == "/frame.hdr":
+                    data = srv.session.hdr_frame()
+                    if data is None:
+                        self._send(404, b"no accumulation to encode", "text/plain")
+                    else:
+                        self._send(200, data, "image/vnd.radiance")
                 elif path == "/state":
                     self._send(200, json.dumps(srv.session.state()).encode(), "application/json")
                 else:

@@ -734,6 +734,46 @@ int pt_preview_png(pt_ctx* c, int32_t iter, pt_png_enc* e, uint8_t* d_out, int64
 int pt_png_enc_profile(pt_png_enc* e, int32_t on);
 int pt_png_enc_profile_read(pt_png_enc* e, float ms[6]);
 
+/* ---- Radiance HDR encoding on the device ------------------------------------- */
+/* The file of pt_encode_hdr, byte for byte, written by kernels from the float accumulator: the same header,
+ * RGBE pixels of rgb / samples, and for 8 <= width <= 32767 the per-channel run-length coding of every scanline
+ * (flat RGBE rows otherwise).  mirror_x = 1 is pt_encode_hdr's orientation (input column x lands at
+ * width-1-x); the default 0 keeps the input's.  The contract covers finite values whose scaled components stay
+ * below 2^31 in magnitude (a negative component beside a positive maximum, whose byte C++ leaves undefined in
+ * pt_encode_hdr, gets the byte the host library's x86 code gives it: in R and G 0 down to -32768, in B the low
+ * byte of the truncation); NaN, infinities and larger values are outside it.  The object
+ * needs no context; pt_hdr_enc_create touches no device (argument errors, PT_ERR_ARG, are found before any
+ * device call) and the scratch is allocated at the first encode; later encodes neither allocate nor
+ * synchronise.  Sizes whose bound reaches 2^31 are refused. */
+typedef struct pt_hdr_params {
+    int32_t mirror_x;     /* default 0 */
+    int32_t reserved[7];
+} pt_hdr_params;
+void pt_hdr_params_default(pt_hdr_params* p);
+typedef struct pt_hdr_enc pt_hdr_enc;
+int pt_hdr_enc_create(int32_t width, int32_t height, const pt_hdr_params* p, pt_hdr_enc** out);
+int pt_hdr_enc_destroy(pt_hdr_enc* e);
+/* The largest file an encode can write: the header + H (4 + 4 (W + ceil(W / 128))) for coded rows, the header
+ * + 4 W H (the file's size) for flat ones.  No device. */
+int64_t pt_hdr_enc_bound(const pt_hdr_enc* e);
+/* Asynchronous on `stream`, device pointers (the caller orders the calls of one object).  d_rgb: the float
+ * accumulator of `samples` samples (finite, > 0).  The file goes to d_out and its size to *d_size (8-byte
+ * aligned); a file that does not fit cap leaves the negated size it needs in *d_size, and no byte at or beyond
+ * d_out + cap is written. */
+int pt_hdr_enc_accum(pt_hdr_enc* e, const float* d_rgb, float samples,
+                     uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream);
+/* A host array, synchronous.  A file larger than cap: PT_ERR_ARG, the size it needs in *size. */
+int pt_hdr_encode_host(int32_t width, int32_t height, const float* rgb, float samples,
+                       const pt_hdr_params* p, uint8_t* out, int64_t cap, int64_t* size);
+/* The context's accumulated image divided by `iter`, encoded by `e` (whose size must be the tile's,
+ * PT_ERR_ARG otherwise; a sharded context, world > 1, is refused).  Orders itself like pt_preview_rgba. */
+int pt_preview_hdr(pt_ctx* c, int32_t iter, pt_hdr_enc* e, uint8_t* d_out, int64_t cap,
+                   int64_t* d_size, void* stream);
+/* Stage timing of an encoder (scripts/hdr_time.py): while on, an encode records events around its stages;
+ * read waits for the last encode and returns the milliseconds of convert, count, scan and emit. */
+int pt_hdr_enc_profile(pt_hdr_enc* e, int32_t on);
+int pt_hdr_enc_profile_read(pt_hdr_enc* e, float ms[4]);
+
 #ifdef __cplusplus
 }
 #endif
