@@ -122,7 +122,8 @@ struct KArgs {
     int32_t bounce;
     int32_t n_fixed;       // >= 0: path count is known on the host (first bounce)
     int32_t* flags;        // [P] survivor flags of the current bounce
-    int32_t* seg;          // [2][kMaxSeg] per-workgroup survivor count | batch iteration << 24 (k_bounce)
+    int32_t* seg;          // [2][kMaxSeg] per-workgroup survivor count | batch iteration << 24 (k_bounce), then
+                           // [2][kMaxSeg][4] the analytic modes' four wave counts of each segment (kSegSubOff)
     int32_t* ibase;        // [kMaxSpp + 1] split pipeline: first dense index of each iteration
     DevStats* stats;
     unsigned long long* emit_slots;   // [64 bounces][emit_stride]: per-workgroup emissive counts
@@ -1675,6 +1676,15 @@ __global__ __launch_bounds__(kBlock) void k_iter_bases(const KArgs A) {
 // logical survivor j lives in the segment s with pre[s] <= j < pre[s+1], at s*chunk + j - pre[s].
 // Concatenating the segments in order is exactly the stable compaction of pathtrace.cu:377-407,
 // so the logical index is the reference's RNG key (pathtrace.cu:315).
+//   Inside a segment the analytic modes (wave_segments) split once more: wave w of the workgroup
+// owns the w-th quarter of its logical range (chunk / 4 = tpb wave-tiles of 64 paths) and writes its
+// survivors, in order, from out[b*chunk + w*chunk/4]; ranks come from the wave's ballot alone, so
+// the tile loop has no barrier.  The four wave counts sub[0..3] go beside the word (their sum is
+// the word's count); survivor r of segment s lives in the sub-segment v with sub[0..v) <= r, at
+// s*chunk + v*chunk/4 + r - sub[0..v).  The consumer scans the words only; a wave reads a
+// segment's four counts (one 16-byte scalar load) when it enters the segment.  Concatenating
+// (b, w) in order is the same stable compaction.  The mesh modes' four waves share every 256-path
+// tile (one barrier per tile): k_traverse / k_traverse4 map their rays through the words alone.
 //   Measured before this design (profiles/r01_*): the decoupled look-back per 256-path tile parked
 // every wave of a workgroup behind wave 0's cross-CU poll — 57% of wave cycles waiting vs 25% in
 // the same trace code without compaction.  Here nothing waits on another workgroup, so the grid
@@ -1692,6 +1702,10 @@ inline int lane_iters(int spp, int lanes, int l) { return spp / lanes + (l < spp
 // Segment words of k_bounce: survivor count | batch iteration << 24 (pt_create bounds chunk < 2^24).
 constexpr int kSegItShift = 24;
 constexpr uint32_t kSegCountMask = (1u << kSegItShift) - 1u;
+// KArgs::seg: the words [2][kMaxSeg], then the four wave counts of every segment [2][kMaxSeg][4].
+constexpr size_t kSegSubOff = (size_t)2 * kMaxSeg;
+constexpr size_t kSegInts = kSegSubOff + (size_t)2 * kMaxSeg * 4;
+typedef int seg4i __attribute__((ext_vector_type(4)));
 
 // The launch's workgroup layout from the iteration starts s_ib[0..spp] (see k_bounce), computed
 // by the whole workgroup (thread t owns iteration t; spp <= kBlock): s_lay = {tpb, nseg, iteration
@@ -1796,6 +1810,10 @@ constexpr int kAnalyticSkip = 3; // 3 no mesh, first bounce: waves with an empty
 constexpr int kAnalyticGM = 4;   // 4 no mesh, more materials or geoms than the LDS tables hold (read from global
                                  //   memory); modes 0 and 3 read both from LDS only (no second inlined shade,
                                  //   no plain per-geom loop for a large table)
+// k_bounce's output layout by mode: the analytic modes' waves each own a quarter of the workgroup's
+// paths and of its output segment (no barrier in the tile loop); the mesh modes' four waves share
+// every 256-path tile (k_traverse / k_traverse4 map rays through the segment words alone).
+constexpr bool wave_segments(int mesh) { return mesh != kMeshInline && mesh != kMeshPre; }
 constexpr int kTravChunk = 256;  // rays per ticket grab
 constexpr int kRefillMin = 16;   // idle lanes that trigger a refill
 constexpr int kTravLdsRows = 32; // LDS stack entries per thread (HybStack; the rest in scratch)
@@ -2506,58 +2524,87 @@ void k_bounce(const KArgs A) {
     const int first = it_base + my_c * chunk;
     const int last = min(__builtin_amdgcn_readfirstlane(s_ib[my_it + 1]), first + chunk);
     const int iter = A.tile.iter_first + my_it;
-    int seg = 0;
-    if (!FIRST) {   // segment of this workgroup's first logical path (binary search, uniform)
+    // Wave-owned layout (wave_segments): wave w owns the quarter [first + w * tpb * 64, ..) of the
+    // workgroup's range, tpb wave-tiles of 64 paths, and writes its survivors in order from
+    // out[b * chunk + w * tpb * 64]: ranks from its own ballot, no barrier in the loop.
+    constexpr bool kWaveSeg = wave_segments(MESH);
+    constexpr int kStep = kWaveSeg ? 64 : kBlock;
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const int wfirst = kWaveSeg ? first + wv * (tpb * 64) : first;
+    const int wlast = kWaveSeg ? min(last, wfirst + tpb * 64) : last;
+    const int li = kWaveSeg ? lane : tid;
+    const int out0 = (int)blockIdx.x * chunk + wv * (tpb * 64);   // (wave-owned layout: the wave's sub-segment)
+    // the wave's current input segment (uniform): its logical range and the running sums of its
+    // producer's first three wave counts, re-read only when the wave leaves the segment
+    int seg = 0, seg_lo = 0, seg_hi = 0, t1 = 0, t2 = 0, t3 = 0;
+    auto enter = [&](const KArgs& A, int s) {
+        seg = s;
+        seg_lo = __builtin_amdgcn_readfirstlane(s_pre[s]);
+        seg_hi = s + 1 < nseg_in ? __builtin_amdgcn_readfirstlane(s_pre[s + 1]) : 0x7fffffff;
+        const seg4i c = as_const(reinterpret_cast<const seg4i*>(A.seg + kSegSubOff))[par * kMaxSeg + s];   // (scalar load)
+        t1 = c.x;
+        t2 = t1 + c.y;
+        t3 = t2 + c.z;
+    };
+    // Physical index of logical path min(wb + lane, wlast - 1) of the wave-tile at wb: survivor r of
+    // segment s sits in the sub-segment of the producer wave v with sub[s][0..v) <= r, at
+    // s * chunk_in + v * (chunk_in / 4) + r - sub[s][0..v).  One pass per distinct segment of the tile.
+    auto map_tile = [&](const KArgs& A, int wb) {
+        const int top = min(wb + 64, wlast);
+        const int i = min(wb + lane, top - 1);
+        if (wb >= seg_hi) {
+            int s = seg + 1;
+            while (s + 1 < nseg_in && __builtin_amdgcn_readfirstlane(s_pre[s + 1]) <= wb) ++s;
+            enter(A, s);
+        }
+        int q = 0;
+        for (;;) {
+            if (i >= seg_lo && i < seg_hi) {
+                const int r = i - seg_lo;
+                const int v = (r >= t1 ? 1 : 0) + (r >= t2 ? 1 : 0) + (r >= t3 ? 1 : 0);
+                const int off = r >= t3 ? t3 : (r >= t2 ? t2 : (r >= t1 ? t1 : 0));
+                q = seg * chunk_in + v * (chunk_in >> 2) + (r - off);
+            }
+            if (seg_hi >= top) break;
+            const int hi = seg_hi;
+            int s = seg + 1;   // (< nseg_in: the last segment's seg_hi ends the loop)
+            while (s + 1 < nseg_in && __builtin_amdgcn_readfirstlane(s_pre[s + 1]) <= hi) ++s;   // empty segments
+            enter(A, s);
+        }
+        return q;
+    };
+    if (!FIRST) {   // segment of the first logical path of this workgroup / wave (binary search, uniform)
         int lo = 0, hi = nseg_in - 1;
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
-            if (s_pre[mid] <= first) lo = mid; else hi = mid - 1;
+            if (s_pre[mid] <= wfirst) lo = mid; else hi = mid - 1;
         }
         seg = lo;
+        if constexpr (kWaveSeg) enter(A, __builtin_amdgcn_readfirstlane(lo));
     }
     uint32_t kept = 0, emit_cnt = 0;
     int k = 0;
-    for (int base = first; base < last; base += kBlock, ++k) {
+    for (int base = wfirst; base < wlast; base += kStep, ++k) {
         const KArgs& A = fresh_args();   // (shadows the parameter: its fields are re-read per tile)
-        const int i = base + tid;
-        if (FIRST && (MESH == 0 || MESH == kAnalyticGM) && A.cmask) {
-            // a tile whose four camera-mask blocks are all empty: every ray misses — shade's miss exit
-            // (colour 0, no random number) without raygen, closest hit or the tile's ballots and
-            // barrier (workgroup-uniform; k stays, so the count buffers keep alternating per barrier)
-            const int lp0 = base - it_base, nb = ((last - it_base) + 63) >> 6;
-            uint32_t any = 0u;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const int b = (lp0 >> 6) + w;
-                any |= b < nb ? A.cmask[b] : 0u;
-            }
-            if (any == 0u) {
-                if (i < last) {
-                    PathReg z;
-                    z.c = F3(0.0f, 0.0f, 0.0f);
-                    z.slot = i;
-                    retire<SPP1>(A, z, my_it);
-                }
-                --k;
-                continue;
-            }
-        }
+        const int i = base + li;
+        int qmap = 0;
+        if constexpr (!FIRST && kWaveSeg) qmap = map_tile(A, base);
         bool alive = false, emitted = false;
         PathReg p;
-        // a wave whose camera rays can hit no geom (camera mask 0): no raygen, no closest hit
-        // (misses draw no random number)
+        // a wave-tile whose camera rays can hit no geom (camera mask 0; one 64-pixel mask block per
+        // wave-tile): no raygen, no closest hit (misses draw no random number)
         bool skip = false;
         if (FIRST && MESH == kAnalyticSkip && A.cmask) {
             const int lp0 = __builtin_amdgcn_readfirstlane(i - it_base);
             skip = lp0 < last - it_base && A.cmask[lp0 >> 6] == 0u;
         }
         if (FIRST && skip) {
-            if (i < last) {   // shade's miss exit: colour 0, retired (no record, no random number)
+            if (i < wlast) {   // shade's miss exit: colour 0, retired (no record, no random number)
                 p.c = F3(0.0f, 0.0f, 0.0f);
                 p.slot = i;
                 retire<SPP1>(A, p, my_it);
             }
-        } else if (i < last) {
+        } else if (i < wlast) {
             int q = i;   // physical index of the path (and of its k_traverse record)
             if (FIRST) {
                 raygen_at(A.cam, A.fl, A.tile, i, my_it, i - it_base, p);   // (a workgroup holds one iteration)
@@ -2571,8 +2618,12 @@ void k_bounce(const KArgs A) {
                 }
 #endif
             } else {
-                const int s = seg_walk(s_pre, nseg_in, seg, i);
-                q = s * chunk_in + (i - s_pre[s]);
+                if constexpr (kWaveSeg) {
+                    q = qmap;
+                } else {
+                    const int s = seg_walk(s_pre, nseg_in, seg, i);
+                    q = s * chunk_in + (i - s_pre[s]);
+                }
                 load_path(A.in, q, A.bounce, p);
             }
             Hit h;
@@ -2657,20 +2708,37 @@ void k_bounce(const KArgs A) {
             }
         }
         emit_cnt += (uint32_t)__popcll(__ballot(emitted));
-        // in-tile ranks: wave ballot + mbcnt, 4 wave counts through LDS (double-buffered, so
-        // one barrier per tile: buffer k&1 was last read two tiles ago, before the last barrier)
         const uint64_t m = __ballot(alive);
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        if (lane == 0) s_wc[k & 1][wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        const uint32_t w0 = s_wc[k & 1][0], w1 = s_wc[k & 1][1], w2 = s_wc[k & 1][2], w3 = s_wc[k & 1][3];
-        const uint32_t before = (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u);
-        if (alive) store_path(A.out, (int)blockIdx.x * chunk + (int)(kept + before + rank), p);
-        kept += (w0 + w1) + (w2 + w3);
-        if (!FIRST) seg = seg_walk(s_pre, nseg_in, seg, min(base + kBlock, last - 1));
+        if constexpr (kWaveSeg) {   // ranks within the wave's own sub-segment: ballot + mbcnt
+            if (alive) store_path(A.out, out0 + (int)(kept + rank), p);
+            kept += (uint32_t)__popcll(m);
+        } else {
+            // in-tile ranks: wave ballot + mbcnt, 4 wave counts through LDS (double-buffered, so
+            // one barrier per tile: buffer k&1 was last read two tiles ago, before the last barrier)
+            if (lane == 0) s_wc[k & 1][wave] = (uint32_t)__popcll(m);
+            __syncthreads();
+            const uint32_t w0 = s_wc[k & 1][0], w1 = s_wc[k & 1][1], w2 = s_wc[k & 1][2], w3 = s_wc[k & 1][3];
+            const uint32_t before = (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u);
+            if (alive) store_path(A.out, (int)blockIdx.x * chunk + (int)(kept + before + rank), p);
+            kept += (w0 + w1) + (w2 + w3);
+        }
+        if (!FIRST && !kWaveSeg) seg = seg_walk(s_pre, nseg_in, seg, min(base + kBlock, last - 1));
     }
-    if (tid == 0) A.seg[(size_t)(par ^ 1) * kMaxSeg + blockIdx.x] = (int32_t)(kept | ((uint32_t)my_it << kSegItShift));
-    flush_emissive(A, emit_cnt, &s_cnt);
+    if constexpr (kWaveSeg) {   // the four wave counts beside the workgroup's word (their sum)
+        if (lane == 0) {
+            s_wc[0][wave] = kept;
+            A.seg[kSegSubOff + ((size_t)(par ^ 1) * kMaxSeg + blockIdx.x) * 4 + wave] = (int32_t)kept;
+        }
+        flush_emissive(A, emit_cnt, &s_cnt);   // (its barriers publish s_wc)
+        if (tid == 0) {
+            const uint32_t sum = (s_wc[0][0] + s_wc[0][1]) + (s_wc[0][2] + s_wc[0][3]);
+            A.seg[(size_t)(par ^ 1) * kMaxSeg + blockIdx.x] = (int32_t)(sum | ((uint32_t)my_it << kSegItShift));
+        }
+    } else {
+        if (tid == 0) A.seg[(size_t)(par ^ 1) * kMaxSeg + blockIdx.x] = (int32_t)(kept | ((uint32_t)my_it << kSegItShift));
+        flush_emissive(A, emit_cnt, &s_cnt);
+    }
 }
 // Stable compaction of the flagged survivors: tile = 256 threads x 4 paths (path order
 // k-major: path = tile*1024 + k*256 + t, so every load/store is wave-contiguous), wave ballot +
@@ -4165,7 +4233,7 @@ int pt_create(const pt_scene* scene, const pt_flags* flags, const pt_shard* shar
     c->max_tiles = (int)((P + kCompactTile - 1) / kCompactTile);   // k_compact_paths tiles
     if (int rc = c->alloc(&A.flags, (size_t)P)) return bail(rc);
     if (int rc = c->alloc(&A.ctl, 2)) return bail(rc);
-    if (int rc = c->alloc(&A.seg, (size_t)2 * kMaxSeg)) return bail(rc);
+    if (int rc = c->alloc(&A.seg, kSegInts)) return bail(rc);
     if (int rc = c->alloc(&A.ibase, (size_t)kMaxSpp + 1)) return bail(rc);
     if (int rc = c->alloc(&A.status, (size_t)2 * c->max_tiles)) return bail(rc);
     if (int rc = c->alloc(&c->stats, 1)) return bail(rc);
@@ -4209,10 +4277,10 @@ int pt_create(const pt_scene* scene, const pt_flags* flags, const pt_shard* shar
                 if (c->mhit[0])
                     if (int rc = c->alloc(&c->mhit[l], cap_l)) return bail(rc);
                 if (int rc = c->alloc(&c->lctl[l], 2)) return bail(rc);
-                if (int rc = c->alloc(&c->lseg[l], (size_t)2 * kMaxSeg)) return bail(rc);
+                if (int rc = c->alloc(&c->lseg[l], kSegInts)) return bail(rc);
                 if (int rc = c->alloc(&c->lemit[l], (size_t)64 * A.emit_stride)) return bail(rc);
                 if ((e = hipMemset(c->lctl[l], 0, 2 * sizeof(Ctl))) != hipSuccess ||
-                    (e = hipMemset(c->lseg[l], 0, (size_t)2 * kMaxSeg * sizeof(int32_t))) != hipSuccess ||
+                    (e = hipMemset(c->lseg[l], 0, kSegInts * sizeof(int32_t))) != hipSuccess ||
                     (e = hipMemset(c->lemit[l], 0, (size_t)64 * A.emit_stride * sizeof(unsigned long long))) != hipSuccess ||
                     (e = hipStreamCreateWithFlags(&c->lane_stream[l], hipStreamNonBlocking)) != hipSuccess ||
                     (e = hipEventCreateWithFlags(&c->ev_join[l], hipEventDisableTiming)) != hipSuccess)
@@ -4225,7 +4293,7 @@ int pt_create(const pt_scene* scene, const pt_flags* flags, const pt_shard* shar
     g_busy_streams.fetch_add(c->busy_streams);
     if ((e = hipMemset(A.image, 0, (size_t)npix * 3 * sizeof(float))) != hipSuccess ||
         (e = hipMemset(A.ctl, 0, 2 * sizeof(Ctl))) != hipSuccess ||
-        (e = hipMemset(A.seg, 0, (size_t)2 * kMaxSeg * sizeof(int32_t))) != hipSuccess ||
+        (e = hipMemset(A.seg, 0, kSegInts * sizeof(int32_t))) != hipSuccess ||
         (e = hipMemset(A.status, 0, (size_t)2 * c->max_tiles * sizeof(uint64_t))) != hipSuccess ||
         (e = hipMemset(c->stats, 0, sizeof(DevStats))) != hipSuccess)
         return bail(pt::fail(PT_ERR_HIP, std::string("hipMemset: ") + hipGetErrorString(e)));
