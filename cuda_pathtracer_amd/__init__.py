@@ -10,7 +10,8 @@ from .pathtrace import (  # noqa: F401
     CUBE, MESH, SPHERE, GuiDataContainer, InitDataContainer, PathTracer, Scene, pathtrace, pathtraceFree,
     pathtraceInit, render, save_image, save_image_hdr, encode_hdr, tonemap, DenoiseParams, denoise,
     DenoiseVarParams, denoise_variance, TemporalParams, TemporalHistory, AdaptiveParams, JpegParams, JpegEncoder, encode_jpeg,
-    PngParams, PngEncoder, encode_png, HdrParams, HdrEncoder, encode_hdr_device)
+    PngParams, PngEncoder, encode_png, HdrParams, HdrEncoder, encode_hdr_device, DisplayParams, DisplayTransform,
+    display_transform, display_tables)
 from . import distributed  # noqa: F401
 from .stream_compaction import (CPU, Efficient, Naive, Thrust, compact_device, live_indices_device,  # noqa: F401
                                 naive_scan_device, partition_device, scan_device, thrust_scan_device)
@@ -21,4 +22,5 @@ __all__ = ["Scene", "PathTracer", "GuiDataContainer", "Efficient", "CPU", "Naive
            "pathtraceFree", "pathtrace",
            "InitDataContainer", "DenoiseParams", "denoise", "DenoiseVarParams", "denoise_variance", "TemporalParams",
            "TemporalHistory", "AdaptiveParams", "JpegParams", "JpegEncoder", "encode_jpeg", "PngParams", "PngEncoder", "encode_png",
-           "HdrParams", "HdrEncoder", "encode_hdr_device", "lib", "LIB_PATH", "NativeLibraryError", "PtError"]
+           "HdrParams", "HdrEncoder", "encode_hdr_device", "DisplayParams", "DisplayTransform", "display_transform",
+           "display_tables", "lib", "LIB_PATH", "NativeLibraryError", "PtError"]

@@ -166,6 +166,27 @@ class HdrParams(C.Structure):
 
 
 assert C.sizeof(HdrParams) == 32
+
+
+class DisplayParams(C.Structure):
+    """pt_display_params; DisplayParams.default() = pt_display_params_default (manual exposure 1, no curve,
+    linear transfer, no mirror: pt_tonemap's conversion)."""
+    _fields_ = [("exposure_mode", C.c_int32), ("exposure", C.c_float), ("key_value", C.c_float),
+                ("compensation_ev", C.c_float), ("min_ev", C.c_float), ("max_ev", C.c_float), ("pct_lo", C.c_int32),
+                ("pct_hi", C.c_int32), ("rate", C.c_int32), ("curve", C.c_int32), ("white", C.c_float),
+                ("transfer", C.c_int32), ("mirror_x", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    @classmethod
+    def default(cls) -> "DisplayParams":
+        p = cls()
+        lib().pt_display_params_default(C.byref(p))
+        return p
+
+
+DISPLAY_MANUAL, DISPLAY_AUTO = 0, 1                                      # PT_DISPLAY_* exposure modes
+DISPLAY_NONE, DISPLAY_REINHARD, DISPLAY_ACES, DISPLAY_HABLE = 0, 1, 2, 3  # curves
+DISPLAY_LINEAR, DISPLAY_SRGB = 0, 1                                      # transfers
+assert C.sizeof(DisplayParams) == 64
 assert C.sizeof(DenoiseParams) == 32 and C.sizeof(DenoiseVarParams) == 32 and C.sizeof(TemporalParams) == 32
 assert C.sizeof(AdaptiveParams) == 32
 assert C.sizeof(Geom) == 272 and C.sizeof(Material) == 48 and C.sizeof(Triangle) == 124
@@ -347,6 +368,17 @@ SIGNATURES = {
     "pt_preview_hdr": (_I, [_P, _I, _P, _P, C.c_int64, _P, _P]),
     "pt_hdr_enc_profile": (_I, [_P, _I]),
     "pt_hdr_enc_profile_read": (_I, [_P, _FP]),
+    "pt_display_params_default": (None, [C.POINTER(DisplayParams)]),
+    "pt_display_create": (_I, [_I, _I, C.POINTER(DisplayParams), C.POINTER(_P)]),
+    "pt_display_destroy": (_I, [_P]),
+    "pt_display_meter": (_I, [_P, _P, _F, _P]),
+    "pt_display_apply": (_I, [_P, _P, _F, _P, _I, _P]),
+    "pt_display_frame": (_I, [_P, _P, _F, _P, _I, _P]),
+    "pt_display_reset": (_I, [_P, _P]),
+    "pt_display_host": (_I, [_I, _I, _P, _F, C.POINTER(DisplayParams), _P, _I]),
+    "pt_display_info": (_I, [_P, _P, _IP, _FP, _IP]),
+    "pt_display_tables": (None, [_P, _P, _FP]),
+    "pt_preview_display": (_I, [_P, _I, _P, _P, _I, _P]),
 }
 
 _lib = None
@@ -370,7 +402,8 @@ def _preload_torch() -> None:
 # pt_ctx_exact_counts, pt_selftest_exact: the A/B against the build before the exact tests' single gate;
 # pt_jpeg_*, pt_preview_jpeg: the A/B against the build before the JPEG encoder; pt_png_*, pt_preview_png: the
 # A/B against the build before the PNG encoder; pt_hdr_*, pt_preview_hdr: the A/B against the build before the
-# HDR encoder).
+# HDR encoder; pt_display_*, pt_preview_display: scripts/display_time.py's A/B against the build before the display
+# transform).
 _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
              "pt_ctx_exact_counts", "pt_selftest_exact",
              "pt_moments_create",
@@ -391,7 +424,10 @@ _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "p
              "pt_png_params_default", "pt_png_enc_create", "pt_png_enc_destroy", "pt_png_enc_bound", "pt_png_enc_pixels",
              "pt_png_enc_accum", "pt_png_encode_host", "pt_preview_png", "pt_png_enc_profile", "pt_png_enc_profile_read",
              "pt_hdr_params_default", "pt_hdr_enc_create", "pt_hdr_enc_destroy", "pt_hdr_enc_bound", "pt_hdr_enc_accum",
-             "pt_hdr_encode_host", "pt_preview_hdr", "pt_hdr_enc_profile", "pt_hdr_enc_profile_read"}
+             "pt_hdr_encode_host", "pt_preview_hdr", "pt_hdr_enc_profile", "pt_hdr_enc_profile_read",
+             "pt_display_params_default", "pt_display_create", "pt_display_destroy", "pt_display_meter", "pt_display_apply",
+             "pt_display_frame", "pt_display_reset", "pt_display_host", "pt_display_info", "pt_display_tables",
+             "pt_preview_display"}
 
 
 def lib() -> C.CDLL:

@@ -29,7 +29,7 @@ ARCH = "gfx950"
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 DEVICE_SRCS = ["sc_kernels.hip", "sc_variants.hip", "pt_kernels.hip", "bvh_build.hip", "pt_denoise.hip",
                "pt_temporal.hip", "pt_adaptive.hip", "pt_enc_common.hip", "pt_jpeg_enc.hip", "pt_png_enc.hip",
-               "pt_hdr_enc.hip"]
+               "pt_hdr_enc.hip", "pt_display.hip"]
 # pt_kernels.hip: no SLP vectorisation.  Packing independent f32 ops into v_pk_* pairs needed
 # register pairs and moves: k_bounce took 79 VGPRs (6 waves/SIMD) instead of 60 (8 waves), and
 # measured 30.8k vs 32.7k Mray/s on the bench (same box, alternating runs; same bits).
@@ -202,6 +202,22 @@ def build_png_chunk_variant(chunk: int = 1024, verbose: bool = False) -> Path:
           "-c", str(CSRC / "pt_png_enc.hip"), "-o", str(obj)], verbose)
     _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(out), str(obj),
           *map(str, other_objs("pt_png_enc.hip")), "-lz"], verbose)
+    return out
+
+
+def build_display_variant(peel: int = 0, verbose: bool = False) -> Path:
+    """Measurement library (not the product): pt_display.hip with another number of bins that a wave of the meter
+    combines by ballot before its LDS atomics (-DPT_DISPLAY_PEEL; the product's is 2), as
+    build/libpt_amd_display_p<peel>.so, which PT_AMD_LIB selects for scripts/display_time.py --meter-only: the
+    measurement behind that choice.  Its histograms are the product's."""
+    build_native(verbose)
+    objdir = PKG / "build"
+    obj = objdir / f"pt_display_p{peel}.o"
+    out = objdir / f"libpt_amd_display_p{peel}.so"
+    _run([HIPCC, "-x", "hip", f"--offload-arch={ARCH}", *COMMON, f"-DPT_DISPLAY_PEEL={peel}", "-I", str(ROOT / "include"),
+          "-c", str(CSRC / "pt_display.hip"), "-o", str(obj)], verbose)
+    _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(out), str(obj),
+          *map(str, other_objs("pt_display.hip")), "-lz"], verbose)
     return out
 
 

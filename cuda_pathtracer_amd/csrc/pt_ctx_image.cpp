@@ -433,4 +433,23 @@ int pt_preview_hdr(pt_ctx* ctx, int32_t iter, pt_hdr_enc* e, uint8_t* d_out, int
                         d_size, stream);
 }
 
+// ---- display bytes ------------------------------------------------------------
+// The same ordering; in auto mode the metering runs first, on the same stream.
+int pt_preview_display(pt_ctx* ctx, int32_t iter, pt_display* d, uint8_t* d_pix, int32_t pixel_stride, void* stream) {
+    CtxHead* c = ctx_head(ctx);
+    if (!c || !d || !d_pix || iter <= 0) return pt::fail(PT_ERR_ARG, "bad argument");
+    if (c->world > 1) return pt::fail(PT_ERR_ARG, "pt_preview_display needs the whole image (world == 1)");
+    int32_t dw = 0, dh = 0, automatic = 0;
+    if (int rc = pt::display_size(d, &dw, &dh, &automatic)) return rc;
+    if (dw != c->W || (int64_t)dw * dh != (int64_t)c->npix)
+        return pt::fail(PT_ERR_ARG, "the display transform and the context's tile differ in size");
+    if (pixel_stride != 3 && pixel_stride != 4) return pt::fail(PT_ERR_ARG, "the pixel stride must be 3 or 4");
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = wait_finalize(c, st)) return rc;
+    if (int rc = automatic ? pt_display_frame(d, c->image, (float)iter, d_pix, pixel_stride, st)
+                           : pt_display_apply(d, c->image, (float)iter, d_pix, pixel_stride, st))
+        return rc;
+    return mark_ctx(c, st);
+}
+
 }  // extern "C"

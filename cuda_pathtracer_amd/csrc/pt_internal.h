@@ -75,6 +75,8 @@ const EncHead* enc_head(const pt_jpeg_enc* e);
 const EncHead* enc_head(const pt_png_enc* e);
 const EncHead* enc_head(const pt_hdr_enc* e);
 void enc_size(const EncHead* e, int32_t* width, int32_t* height);
+// pt_display (pt_display.hip): the image size it was created for and whether its exposure is metered
+int display_size(const pt_display* d, int32_t* width, int32_t* height, int32_t* automatic);
 
 inline float bits_to_float(int32_t v) {
     float f;

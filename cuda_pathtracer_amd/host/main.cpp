@@ -5,7 +5,11 @@
 //
 //   pathtracer_amd SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise]
 //                  [--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png]
-//                  [--device-hdr]
+//                  [--device-hdr] [--tonemap none|reinhard|aces|hable] [--exposure EV|auto] [--srgb]
+// --tonemap, --exposure, --srgb: any of them additionally writes ...samp.display.png, the accumulator through the
+// display transform (pt_preview_display, DESIGN.md §17: the tone curve, an exposure of EV stops or a metered one,
+// the sRGB transfer), x-mirrored like every saved image and written by the device PNG encoder from the device
+// bytes.  The other files keep their names and bytes.
 // --device-hdr, with --hdr, writes the main .hdr file on the device (pt_preview_hdr: the same name and the same
 // bytes; the denoised and adaptive .hdr files stay on the host writer).
 // --device-png writes the final PNG on the device (pt_preview_png with pt_tonemap's conversion and the x
@@ -23,6 +27,7 @@
 // with --denoise-variance also its variance-filtered version as ...samp.adaptive.denoised-var.png, and
 // reports the samples per block and the segments traced.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -123,6 +128,36 @@ std::string saveHdrDevice(const Scene& scene, const std::string& dir, const std:
         return pt_preview_hdr(pathtraceContext(), iteration, enc, d_out, cap, d_size, nullptr);
     });
     pt_hdr_enc_destroy(enc);
+    return filename;
+}
+
+// --tonemap, --exposure, --srgb: ...samp.display.png, the display transform's bytes through the device PNG encoder.
+std::string saveDisplayDevice(const Scene& scene, const std::string& dir, const std::string& start, int iteration,
+                              const pt_display_params& dprm) {
+    const int W = scene.state.camera.res[0], H = scene.state.camera.res[1];
+    auto die = [](const char* what) {
+        std::fprintf(stderr, "saveImage (display): %s: %s\n", what, pt_last_error());
+        std::exit(EXIT_FAILURE);
+    };
+    pt_display* disp = nullptr;
+    if (pt_display_create(W, H, &dprm, &disp)) die("display transform");
+    pt_png_params prm;
+    pt_png_params_default(&prm);   // (no mirror: the display transform's bytes are mirrored already)
+    pt_png_enc* enc = nullptr;
+    if (pt_png_enc_create(W, H, &prm, &enc)) die("encoder");
+    uint8_t* d_pix = nullptr;
+    if (hipMalloc((void**)&d_pix, (size_t)W * H * 3) != hipSuccess) {
+        std::fprintf(stderr, "saveImage (display): out of device memory\n");
+        std::exit(EXIT_FAILURE);
+    }
+    if (pt_preview_display(pathtraceContext(), iteration, disp, d_pix, 3, nullptr)) die("pt_preview_display");
+    const std::string filename = saveDeviceFile(scene, dir, start, iteration, ".display.png", pt_png_enc_bound(enc),
+                                                [&](uint8_t* d_out, int64_t cap, int64_t* d_size) {
+        return pt_png_enc_pixels(enc, d_pix, 3, d_out, cap, d_size, nullptr);
+    });
+    pt_png_enc_destroy(enc);
+    pt_display_destroy(disp);
+    (void)hipFree(d_pix);
     return filename;
 }
 
@@ -231,7 +266,8 @@ int main(int argc, char** argv) {
     const std::string startTimeString = currentTimeString();
     if (argc < 2) {
         std::printf("Usage: %s SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise] "
-                    "[--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png] [--device-hdr]\n", argv[0]);
+                    "[--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png] [--device-hdr] "
+                    "[--tonemap none|reinhard|aces|hable] [--exposure EV|auto] [--srgb]\n", argv[0]);
         return 1;
     }
     const char* sceneFile = argv[1];
@@ -241,6 +277,10 @@ int main(int argc, char** argv) {
     bool device_png = false, device_hdr = false;
     float adaptive_threshold = 0.0f;
     int adaptive_every = 4;
+    bool display = false;
+    pt_display_params dprm;
+    pt_display_params_default(&dprm);
+    dprm.mirror_x = 1;
     for (int i = 2; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--iterations") && i + 1 < argc) iterations = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out_dir = argv[++i];
@@ -254,6 +294,36 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--aov") && i + 1 < argc) { aov_dir = argv[++i]; aov = true; }
         else if (!std::strcmp(argv[i], "--adaptive") && i + 1 < argc) { adaptive_threshold = (float)std::atof(argv[++i]); adaptive = true; }
         else if (!std::strcmp(argv[i], "--adaptive-every") && i + 1 < argc) adaptive_every = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--tonemap") && i + 1 < argc) {
+            const char* names[4] = {"none", "reinhard", "aces", "hable"};   // PT_DISPLAY_NONE .. PT_DISPLAY_HABLE
+            int k = 0;
+            ++i;
+            while (k < 4 && std::strcmp(argv[i], names[k])) ++k;
+            if (k == 4) {
+                std::fprintf(stderr, "--tonemap %s: none, reinhard, aces or hable\n", argv[i]);
+                return 1;
+            }
+            dprm.curve = k;
+            display = true;
+        } else if (!std::strcmp(argv[i], "--exposure") && i + 1 < argc) {
+            ++i;
+            if (!std::strcmp(argv[i], "auto")) {
+                dprm.exposure_mode = PT_DISPLAY_AUTO;
+            } else {
+                char* end = nullptr;
+                const double ev = std::strtod(argv[i], &end);
+                if (end == argv[i] || *end || !(ev >= -64.0 && ev <= 64.0)) {
+                    std::fprintf(stderr, "--exposure %s: a number of stops in -64 .. 64, or auto\n", argv[i]);
+                    return 1;
+                }
+                dprm.exposure_mode = PT_DISPLAY_MANUAL;
+                dprm.exposure = (float)std::exp2(ev);
+            }
+            display = true;
+        } else if (!std::strcmp(argv[i], "--srgb")) {
+            dprm.transfer = PT_DISPLAY_SRGB;
+            display = true;
+        }
         else {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
             return 1;
@@ -294,6 +364,7 @@ int main(int argc, char** argv) {
     if (hdr)
         std::printf("wrote %s\n", device_hdr ? saveHdrDevice(*scene, out_dir, startTimeString, iteration).c_str()
                                              : saveImage(*scene, out_dir, startTimeString, iteration, true).c_str());
+    if (display) std::printf("wrote %s\n", saveDisplayDevice(*scene, out_dir, startTimeString, iteration, dprm).c_str());
     if (denoise) {
         std::vector<float> dn((size_t)scene->state.camera.res[0] * scene->state.camera.res[1] * 3);
         pt_denoise_params prm;

@@ -20,8 +20,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, HdrParams, JpegParams, PngParams, TemporalParams,  # noqa: F401
-                      check_pt, lib)
+from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, DisplayParams, HdrParams, JpegParams, PngParams,  # noqa: F401
+                      TemporalParams, check_pt, lib)
 
 SPHERE, CUBE, MESH = 0, 1, 2
 
@@ -426,14 +426,33 @@ class PathTracer:
         check_pt(entry(self._h, int(iteration), encoder._h, out.data_ptr(), encoder.cap, size.data_ptr(), _stream_ptr(stream)))
         return encoder._read(stream)
 
-    def preview_jpeg(self, iteration: int, encoder: "JpegEncoder", stream=None) -> bytes:
+    def preview_display(self, iteration: int, display: "DisplayTransform", dst_ptr: int, pixel_stride: int = 4,
+                        stream=None) -> None:
+        """The accumulated image of `iteration` iterations through `display` (pt_preview_display: metered first in
+        auto mode) as RGB8 / RGBA8 bytes at the device pointer dst_ptr; asynchronous."""
+        check_pt(lib().pt_preview_display(self._h, int(iteration), display._h, C.c_void_p(dst_ptr), int(pixel_stride),
+                                          _stream_ptr(stream)))
+
+    def _preview_displayed(self, iteration: int, encoder: "_Encoder", display: "DisplayTransform", stream) -> bytes:
+        """preview_display into the device pixels `encoder` keeps, then its pixels entry: only the file crosses."""
+        pix = encoder._pixel_buffer()
+        self.preview_display(iteration, display, pix.data_ptr(), 4, stream)
+        return encoder.encode(pix.data_ptr(), pixel_stride=4, stream=stream)
+
+    def preview_jpeg(self, iteration: int, encoder: "JpegEncoder", stream=None, display: "DisplayTransform | None" = None) -> bytes:
         """The accumulated image of `iteration` iterations as preview_rgba converts it, as a JPEG file
-        encoded on the device by `encoder` (pt_preview_jpeg): only the file crosses to the host."""
+        encoded on the device by `encoder` (pt_preview_jpeg): only the file crosses to the host.  display: a
+        DisplayTransform that converts it instead, still on the device."""
+        if display is not None:
+            return self._preview_displayed(iteration, encoder, display, stream)
         return self._preview_file(lib().pt_preview_jpeg, iteration, encoder, stream)
 
-    def preview_png(self, iteration: int, encoder: "PngEncoder", stream=None) -> bytes:
+    def preview_png(self, iteration: int, encoder: "PngEncoder", stream=None, display: "DisplayTransform | None" = None) -> bytes:
         """The accumulated image of `iteration` iterations as a PNG file written on the device by `encoder`
-        (pt_preview_png), converted as the encoder's params.conv says: only the file crosses to the host."""
+        (pt_preview_png), converted as the encoder's params.conv says: only the file crosses to the host.  display:
+        a DisplayTransform that converts it instead, still on the device."""
+        if display is not None:
+            return self._preview_displayed(iteration, encoder, display, stream)
         return self._preview_file(lib().pt_preview_png, iteration, encoder, stream)
 
     def save_png(self, path: str, iteration: int) -> str:
@@ -742,7 +761,7 @@ class _Encoder:
     def __init__(self, width: int, height: int, params=None, cap: int | None = None):
         self.width, self.height = int(width), int(height)
         self._h = C.c_void_p()
-        self._out = self._size = None
+        self._out = self._size = self._pix = None
         create, bound, self._destroy, self._pixels, self._accum = self._entry(lib())
         prm = params if params is not None else self._params.default()
         check_pt(create(self.width, self.height, C.byref(prm), C.byref(self._h)))
@@ -753,7 +772,7 @@ class _Encoder:
         if self._h is not None and self._h.value:
             check_pt(self._destroy(self._h))
         self._h = None
-        self._out = self._size = None
+        self._out = self._size = self._pix = None
 
     def __del__(self):
         try:
@@ -767,6 +786,13 @@ class _Encoder:
             self._out = torch.empty(max(self.cap, 1), dtype=torch.uint8, device="cuda")
             self._size = torch.zeros(1, dtype=torch.int64, device="cuda")
         return self._out, self._size
+
+    def _pixel_buffer(self):
+        """Device RGBA8 pixels of the encoder's size (PathTracer.preview_jpeg / preview_png with display=)."""
+        import torch
+        if self._pix is None:
+            self._pix = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device="cuda")
+        return self._pix
 
     def _read(self, stream) -> bytes:
         """The size first, then that many bytes."""
@@ -892,6 +918,109 @@ def encode_png(rgb8: np.ndarray, filter=None, block_bytes: int | None = None, mi
         n_f = h * (1 + 3 * w)
         return (9 * n_f + 10 * -(-n_f // max(prm.block_bytes, 1)) + 7) // 8 + 63
     return _encode_host(lib().pt_png_encode_host, rgb8, prm, bound)
+
+
+class DisplayTransform:
+    """pt_display: the display transform on the device for (height, width) accumulators; params: a
+    DisplayParams (default: pt_tonemap's conversion without its mirror).  meter / apply / frame take an
+    (H, W, 3) float32 array or tensor of `samples` samples, or a device pointer (int) to one."""
+
+    def __init__(self, width: int, height: int, params: "N.DisplayParams | None" = None):
+        self.width, self.height = int(width), int(height)
+        self._h = C.c_void_p()
+        prm = params if params is not None else N.DisplayParams.default()
+        check_pt(lib().pt_display_create(self.width, self.height, C.byref(prm), C.byref(self._h)))
+
+    def free(self) -> None:
+        if self._h is not None and self._h.value:
+            check_pt(lib().pt_display_destroy(self._h))
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def _source(self, src):
+        """(device pointer, what keeps it alive)."""
+        import torch
+        if isinstance(src, int):
+            return src, None
+        t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src))
+        if t.dtype != torch.float32 or tuple(t.shape) != (self.height, self.width, 3):
+            raise ValueError(f"source {tuple(t.shape)} {t.dtype}: expected ({self.height}, {self.width}, 3) torch.float32")
+        keep = t.contiguous().cuda()
+        return keep.data_ptr(), keep
+
+    def meter(self, src, samples: float, stream=None) -> None:
+        """pt_display_meter: the histogram of src / samples and the exposure state's step; asynchronous."""
+        ptr, keep = self._source(src)
+        check_pt(lib().pt_display_meter(self._h, C.c_void_p(ptr), float(samples), _stream_ptr(stream)))
+        if keep is not None:
+            self._wait(stream)
+
+    def _wait(self, stream) -> None:
+        import torch
+        if stream is None:   # (the null stream: not torch's current one)
+            torch.cuda.synchronize()
+        else:
+            (stream if hasattr(stream, "synchronize") else torch.cuda.ExternalStream(int(stream))).synchronize()
+
+    def _bytes(self, entry, src, samples: float, dst_ptr, pixel_stride: int, stream):
+        import torch
+        ptr, keep = self._source(src)
+        out = None
+        if dst_ptr is None:
+            out = torch.empty((self.height, self.width, int(pixel_stride)), dtype=torch.uint8, device="cuda")
+            dst_ptr = out.data_ptr()
+        check_pt(entry(self._h, C.c_void_p(ptr), float(samples), C.c_void_p(int(dst_ptr)), int(pixel_stride), _stream_ptr(stream)))
+        if out is None and keep is None:
+            return None   # (device to device: asynchronous)
+        self._wait(stream)
+        return out.cpu().numpy() if out is not None else None
+
+    def apply(self, src, samples: float, dst_ptr: int | None = None, pixel_stride: int = 3, stream=None):
+        """pt_display_apply: the bytes to the device pointer dst_ptr (asynchronous when src is a pointer too), or
+        without one returned as an (H, W, pixel_stride) uint8 array."""
+        return self._bytes(lib().pt_display_apply, src, samples, dst_ptr, pixel_stride, stream)
+
+    def frame(self, src, samples: float, dst_ptr: int | None = None, pixel_stride: int = 3, stream=None):
+        """pt_display_frame: meter, then apply."""
+        return self._bytes(lib().pt_display_frame, src, samples, dst_ptr, pixel_stride, stream)
+
+    def reset(self, stream=None) -> None:
+        """The next metering jumps to its target (pt_display_reset)."""
+        check_pt(lib().pt_display_reset(self._h, _stream_ptr(stream)))
+
+    def info(self) -> dict:
+        """pt_display_info (synchronous): hist (257 uint32, as last resolved; [256]: the uncounted pixels), e (the
+        exposure in 1/256 octave), mult (the multiplier apply uses) and metered."""
+        hist = np.zeros(257, np.uint32)
+        e, mult, metered = C.c_int32(), C.c_float(), C.c_int32()
+        check_pt(lib().pt_display_info(self._h, hist.ctypes.data, C.byref(e), C.byref(mult), C.byref(metered)))
+        return {"hist": hist, "e": int(e.value), "mult": float(mult.value), "metered": int(metered.value)}
+
+
+def display_tables() -> dict:
+    """pt_display_tables (no device): srgb (256 float32 thresholds, [0] unused), pow2 (256 float32) and hable_white."""
+    srgb, pow2 = np.zeros(256, np.float32), np.zeros(256, np.float32)
+    hw = C.c_float()
+    lib().pt_display_tables(srgb.ctypes.data, pow2.ctypes.data, C.byref(hw))
+    return {"srgb": srgb, "pow2": pow2, "hable_white": np.float32(hw.value)}
+
+
+def display_transform(acc: np.ndarray, samples: float, params: "N.DisplayParams | None" = None, pixel_stride: int = 3) -> np.ndarray:
+    """An (H, W, 3) float32 host accumulator of `samples` samples through the display transform on the device
+    (pt_display_host; auto mode meters this one image) -> (H, W, pixel_stride) uint8."""
+    img = np.ascontiguousarray(acc, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"image shape {img.shape}: expected (H, W, 3)")
+    prm = params if params is not None else N.DisplayParams.default()
+    out = np.empty((img.shape[0], img.shape[1], int(pixel_stride)), np.uint8)
+    check_pt(lib().pt_display_host(img.shape[1], img.shape[0], img.ctypes.data, float(samples), C.byref(prm), out.ctypes.data,
+                                   int(pixel_stride)))
+    return out
 
 
 def tonemap(image: np.ndarray, samples: float) -> np.ndarray:

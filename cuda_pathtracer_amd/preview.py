@@ -18,6 +18,8 @@ render process:
                    /frame.png is written on the device too (pt_preview_png): the
                    same pixels, another file.  GET /frame.hdr is the current accumulation as a
                    Radiance HDR file, always written on the device (pt_preview_hdr).
+                   The panel's Display settings (tone curve, exposure, metering, sRGB) send the
+                   frames through the display transform on the device.
 
     python -m cuda_pathtracer_amd.preview SCENE.json [--port 8080]   (then open the printed URL)
 
@@ -39,8 +41,10 @@ from pathlib import Path
 
 import numpy as np
 
-from .pathtrace import (DenoiseVarParams, GuiDataContainer, HdrEncoder, HdrParams, JpegEncoder, PathTracer, PngEncoder, Scene,
-                        TemporalHistory, _jpeg_params, _png_params, encode_jpeg, encode_png, save_image, tonemap)
+from . import _native as N
+from .pathtrace import (DenoiseVarParams, DisplayParams, DisplayTransform, GuiDataContainer, HdrEncoder, HdrParams, JpegEncoder,
+                        PathTracer, PngEncoder, Scene, TemporalHistory, _jpeg_params, _png_params, display_transform, encode_jpeg,
+                        encode_png, save_image, tonemap)
 
 F32 = np.float32
 PI = F32(3.1415926535897932384626422832795028841971)   # utilities.h PI (a float)
@@ -52,6 +56,10 @@ RELEASE, PRESS = 0, 1
 VISUAL_SETTINGS = ("SSAA", "DoF", "aperture", "focal_len")
 GENERAL_SETTINGS = ("russianRoulette", "sortbyMaterial", "useThrustPartition")
 SLIDERS = {"aperture": (0.1, 1.0), "focal_len": (10.0, 80.0)}   # ImGui::SliderFloat ranges
+# panel settings of the display transform: display only, like `denoise`
+TONEMAPS = {"none": N.DISPLAY_NONE, "reinhard": N.DISPLAY_REINHARD, "aces": N.DISPLAY_ACES, "hable": N.DISPLAY_HABLE}
+EXPOSURE_EV = (-16.0, 16.0)
+AUTO_EXPOSURE_RATE = 32   # of 256: the share of the way to the metered target a frame goes
 
 
 def _normalize(v: np.ndarray) -> np.ndarray:   # glm::normalize: v * inversesqrt(dot(v, v))
@@ -74,7 +82,14 @@ class PreviewSession:
     png_device: False (the default: /frame.png is png_bytes of the PBO, on the host), or True: the frame's
     PNG is written on the device (png_frame: pt_preview_png for a raw frame, encode_png for the host arrays
     of the denoised paths), with display_rgb()'s pixels; as in JPEG mode the PBO of a raw frame is read only
-    when display_rgb() asks for it."""
+    when display_rgb() asks for it.
+
+    tonemap, exposure_ev, auto_exposure, srgb (panel settings, all off by default): the frames go through the
+    session's DisplayTransform instead of the linear clip: raw frames on the device
+    (pt_preview_display, into the encoders' pixel entries in JPEG mode and with png_device), denoised and temporal
+    frames through display_transform on their host arrays.  With auto_exposure the exposure is metered every frame
+    and adapts over frames (exposure_ev is then the compensation).  With all four at their defaults every path is
+    the one described above."""
 
     def __init__(self, scene: Scene, gui: GuiDataContainer | None = None, out_dir: str | None = None,
                  tracer_factory=None, read_preview=None, history_factory=None, jpeg: int | None = None,
@@ -130,6 +145,8 @@ class PreviewSession:
         self.png_device = bool(png_device)
         self._png_enc = None
         self._hdr_enc = None         # /frame.hdr's encoder, made at the first request
+        self.tonemap, self.exposure_ev, self.auto_exposure, self.srgb = "none", 0.0, False, False
+        self._display = None         # the session's DisplayTransform, made when a frame needs it
         self._raw_frame = False      # the current frame is the context's accumulator as pt_preview_rgba converts it
         self.jpeg_bytes = b""        # the current frame's file (JPEG mode)
         self.frame_serial = 0        # counts the files: /stream.mjpg sends each once
@@ -199,6 +216,19 @@ class PreviewSession:
                 self.denoise_temporal = bool(value)
                 if not self.denoise_temporal:
                     self._free_history()
+            elif name == "tonemap":   # display only, as are the three below: no restart, S is untouched
+                if value not in TONEMAPS:
+                    raise ValueError(f"tonemap {value!r}: one of {', '.join(TONEMAPS)}")
+                self._set_display(tonemap=value)
+            elif name == "exposure_ev":
+                if isinstance(value, (bool, str)) or value is None:
+                    raise ValueError(f"exposure_ev {value!r}: a number of stops")
+                ev = float(value)
+                if not EXPOSURE_EV[0] <= ev <= EXPOSURE_EV[1]:   # (false for NaN)
+                    raise ValueError(f"exposure_ev {value!r}: {EXPOSURE_EV[0]} .. {EXPOSURE_EV[1]}")
+                self._set_display(exposure_ev=ev)
+            elif name in ("auto_exposure", "srgb"):
+                self._set_display(**{name: bool(value)})
             elif name in GENERAL_SETTINGS or name in ("SSAA", "DoF"):
                 setattr(self.gui, name, bool(value))
             elif name in SLIDERS:
@@ -209,6 +239,36 @@ class PreviewSession:
             if name in VISUAL_SETTINGS:
                 self.visual_changed = True
 
+    # ---- the display transform ------------------------------------------------
+    def _set_display(self, **kw) -> None:
+        if any(getattr(self, k) != v for k, v in kw.items()):
+            for k, v in kw.items():
+                setattr(self, k, v)
+            self._free_display()   # (its parameters are fixed at creation: the next frame makes another)
+
+    def _display_on(self) -> bool:
+        return self.tonemap != "none" or self.exposure_ev != 0.0 or self.auto_exposure or self.srgb
+
+    def _display_params(self) -> DisplayParams:
+        """The bytes land in the PBO's orientation (the encoders and display_rgb mirror x)."""
+        p = DisplayParams.default()
+        p.curve, p.transfer = TONEMAPS[self.tonemap], N.DISPLAY_SRGB if self.srgb else N.DISPLAY_LINEAR
+        if self.auto_exposure:
+            p.exposure_mode, p.rate, p.compensation_ev = N.DISPLAY_AUTO, AUTO_EXPOSURE_RATE, self.exposure_ev
+        else:
+            p.exposure = 2.0 ** self.exposure_ev
+        return p
+
+    def _display_obj(self) -> DisplayTransform:
+        if self._display is None:
+            self._display = DisplayTransform(self.width, self.height, self._display_params())
+        return self._display
+
+    def _free_display(self) -> None:
+        if self._display is not None:
+            self._display.free()
+            self._display = None
+
     # ---- runCuda (main.cpp:114-168) -----------------------------------------------------------
     def run_cuda(self) -> None:
         with self.lock:
@@ -217,6 +277,8 @@ class PreviewSession:
             t0 = time.perf_counter()
             if self.visual_changed and self._history is not None:
                 self._history.reset()   # (another image: a camera change alone keeps the history)
+            if self.visual_changed and self._display is not None:
+                self._display.reset()   # (likewise: the next metering jumps to its target)
             if self.camchanged or self.visual_changed:
                 self.iteration = 0
                 self.scene.set_orbit(float(self.phi), float(self.theta), float(self.zoom), self.look_at)
@@ -271,12 +333,17 @@ class PreviewSession:
         import torch
         if self._dbuf is None:
             self._dbuf = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device="cuda")
-        ctx.preview_rgba(it, self._dbuf.data_ptr())   # (the render's stream: NULL)
+        if self._display_on():
+            ctx.preview_display(it, self._display_obj(), self._dbuf.data_ptr(), 4)
+        else:
+            ctx.preview_rgba(it, self._dbuf.data_ptr())   # (the render's stream: NULL)
         return self._dbuf.cpu().numpy()
 
     def _jpeg_preview(self) -> bytes:
         if self._enc is None:
             self._enc = JpegEncoder(self.width, self.height, _jpeg_params(self.jpeg, "420", True))
+        if self._display_on():
+            return self.ctx.preview_jpeg(self.iteration, self._enc, display=self._display_obj())
         return self.ctx.preview_jpeg(self.iteration, self._enc)
 
     def png_frame(self) -> bytes:
@@ -287,6 +354,8 @@ class PreviewSession:
             if self._raw_frame and self.ctx is not None and self.iteration > 0:
                 if self._png_enc is None:
                     self._png_enc = PngEncoder(self.width, self.height, _png_params(mirror_x=True))
+                if self._display_on():
+                    return self.ctx.preview_png(self.iteration, self._png_enc, display=self._display_obj())
                 return self.ctx.preview_png(self.iteration, self._png_enc)
             self._current_rgba()
             return encode_png(self.rgba, mirror_x=True)
@@ -323,7 +392,7 @@ class PreviewSession:
     def _pbo_of(self, img: np.ndarray) -> np.ndarray:
         self._rgba_current = True
         self._raw_frame = False
-        rgb = tonemap(img, 1.0)[:, ::-1]
+        rgb = display_transform(img, 1.0, self._display_params()) if self._display_on() else tonemap(img, 1.0)[:, ::-1]
         out = np.zeros((self.height, self.width, 4), np.uint8)
         out[..., :3] = rgb
         return out
@@ -381,6 +450,7 @@ class PreviewSession:
             if self._hdr_enc is not None:
                 self._hdr_enc.free()
                 self._hdr_enc = None
+            self._free_display()
             self.frame_ready.notify_all()
 
     # ---- what the window shows ----------------------------------------------------------------
@@ -406,7 +476,8 @@ class PreviewSession:
                 "ms_per_frame": ft * 1e3, "fps": (1.0 / ft) if ft > 0 else 0.0,
                 "settings": {**{k: getattr(self.gui, k) for k in GENERAL_SETTINGS + VISUAL_SETTINGS},
                              "denoise": self.denoise, "denoise_variance": self.denoise_variance,
-                             "denoise_temporal": self.denoise_temporal},
+                             "denoise_temporal": self.denoise_temporal, "tonemap": self.tonemap,
+                             "exposure_ev": self.exposure_ev, "auto_exposure": self.auto_exposure, "srgb": self.srgb},
                 "camera": {"phi": float(self.phi), "theta": float(self.theta), "zoom": float(self.zoom),
                            "look_at": [float(v) for v in self.look_at],
                            "position": [float(v) for v in cam.position[:3]]},
@@ -454,6 +525,11 @@ fieldset{border:1px solid #555;margin:0 0 8px 0} input[type=range]{width:160px}<
 <label><input type="checkbox" id="denoise"> Show the denoised image (edge-avoiding a-trous filter)</label><br>
 <label><input type="checkbox" id="denoise_variance"> Show the variance-guided denoised image (tracks per-pixel variance)</label><br>
 <label><input type="checkbox" id="denoise_temporal"> Keep the denoiser's history across camera moves (temporal reprojection)</label></fieldset>
+<fieldset><legend>Display</legend>
+<label>Tone curve <select id="tonemap"><option>none</option><option>reinhard</option><option>aces</option><option>hable</option></select></label><br>
+<label>Exposure (stops) <input type="range" id="exposure_ev" min="-8" max="8" step="0.25"></label><br>
+<label><input type="checkbox" id="auto_exposure"> Meter the exposure (the slider compensates)</label><br>
+<label><input type="checkbox" id="srgb"> sRGB transfer</label></fieldset>
 <fieldset><legend>Visual settings</legend>
 <label><input type="checkbox" id="SSAA"> Enable stochastic sampled antialiasing</label><br>
 <label><input type="checkbox" id="DoF"> Enable DoF effects</label><br>
@@ -472,9 +548,10 @@ img.addEventListener('mousemove',e=>{const p=pos(e);post({kind:'move',x:p.x,y:p.
 img.addEventListener('contextmenu',e=>e.preventDefault());
 window.addEventListener('keydown',e=>{const k=e.key==='Escape'?'ESCAPE':e.key===' '?'SPACE':e.key.toUpperCase();
  if(['ESCAPE','SPACE','S'].includes(k)){e.preventDefault();post({kind:'key',key:k});}});
-for(const id of ['russianRoulette','sortbyMaterial','useThrustPartition','denoise','denoise_variance','denoise_temporal','SSAA','DoF'])
+for(const id of ['russianRoulette','sortbyMaterial','useThrustPartition','denoise','denoise_variance','denoise_temporal','SSAA','DoF','auto_exposure','srgb'])
  document.getElementById(id).addEventListener('change',e=>post({kind:'setting',name:id,value:e.target.checked}));
-for(const id of ['aperture','focal_len'])
+document.getElementById('tonemap').addEventListener('change',e=>post({kind:'setting',name:'tonemap',value:e.target.value}));
+for(const id of ['aperture','focal_len','exposure_ev'])
  document.getElementById(id).addEventListener('input',e=>post({kind:'setting',name:id,value:parseFloat(e.target.value)}));
 async function poll(){try{const s=await (await fetch('/state')).json();
  document.getElementById('title').textContent=s.title;document.title=s.title;
@@ -585,7 +662,7 @@ class PreviewServer:
         s = self.session
         with s.lock:
             it = s.iteration
-            if self._png[0] != it:
+            if self._png[0] != it:   # (a display setting shows from the next iteration's frame on)
                 self._png = (it, s.png_frame() if s.png_device else png_bytes(s.display_rgb()))
             return self._png[1]
 

@@ -774,6 +774,72 @@ int pt_preview_hdr(pt_ctx* c, int32_t iter, pt_hdr_enc* e, uint8_t* d_out, int64
 int pt_hdr_enc_profile(pt_hdr_enc* e, int32_t on);
 int pt_hdr_enc_profile_read(pt_hdr_enc* e, float ms[4]);
 
+/* ---- display transform on the device ------------------------------------------ */
+/* The float accumulator to display bytes (RGB8 or RGBA8 with alpha 0): an exposure multiplier, manual or
+ * metered from a luminance histogram, a tone curve, the clamp to 0..1 and a transfer function.  The bytes
+ * are an exact function of the input floats (DESIGN.md §17 is the definition; tests/display_ref.py restates
+ * it in numpy); the defaults reproduce pt_tonemap's conversion.  The object needs no context;
+ * pt_display_create touches no device (argument errors, PT_ERR_ARG, are found before any device call), the
+ * scratch is allocated at first use, and later calls neither allocate nor synchronise. */
+#define PT_DISPLAY_MANUAL 0
+#define PT_DISPLAY_AUTO 1
+#define PT_DISPLAY_NONE 0
+#define PT_DISPLAY_REINHARD 1 /* extended Reinhard, parameter `white` */
+#define PT_DISPLAY_ACES 2     /* Narkowicz's rational fit */
+#define PT_DISPLAY_HABLE 3    /* Uncharted 2, W = 11.2 */
+#define PT_DISPLAY_LINEAR 0   /* (uint8_t)(c * 255.f): pt_tonemap's byte */
+#define PT_DISPLAY_SRGB 1     /* the correctly rounded sRGB byte, floor(255 oetf(c) + 0.5) */
+typedef struct pt_display_params {
+    int32_t exposure_mode;  /* default PT_DISPLAY_MANUAL */
+    float exposure;         /* the multiplier in manual mode, finite and > 0, default 1 */
+    float key_value;        /* auto: the luminance the metered level is mapped to, default 0.18 */
+    float compensation_ev;  /* auto: added to the target, in stops, -64..64, default 0 */
+    float min_ev, max_ev;   /* auto: limits of the exposure in stops, -64 <= min <= max <= 64, default -8, 8 */
+    int32_t pct_lo, pct_hi; /* auto: the ranks metered, in 1/1024 of the counted pixels, 0 <= lo < hi <= 1024,
+                             * default 102, 922 */
+    int32_t rate;           /* auto: the share of the way to the target a metering goes, in 1/256, 1..256,
+                             * default 256 (no adaptation) */
+    int32_t curve;          /* default PT_DISPLAY_NONE */
+    float white;            /* PT_DISPLAY_REINHARD: the radiance mapped to 1, finite and > 0, default 4 */
+    int32_t transfer;       /* default PT_DISPLAY_LINEAR */
+    int32_t mirror_x;       /* default 0; 1: input column x lands at width-1-x */
+    int32_t reserved[3];
+} pt_display_params;
+void pt_display_params_default(pt_display_params* p);
+typedef struct pt_display pt_display;
+int pt_display_create(int32_t width, int32_t height, const pt_display_params* p, pt_display** out);
+int pt_display_destroy(pt_display* d);
+/* Asynchronous on `stream`, device pointers (the caller orders the calls of one object); nothing waits for
+ * the host.  d_rgb: the float accumulator of `samples` samples (finite, > 0).
+ * meter: the luminance histogram of d_rgb / samples, then the exposure state's step towards its target.
+ *        The first metering after create or reset jumps to the target; an image without a counted pixel
+ *        changes nothing.
+ * apply: the bytes to d_pix (pixel_stride 3 or 4, width * height * pixel_stride bytes, no byte beyond them);
+ *        auto mode reads the multiplier the last metering left on the device (1 before any).  d_pix must
+ *        not alias d_rgb.
+ * frame: meter, then apply.   reset: the next metering jumps again. */
+int pt_display_meter(pt_display* d, const float* d_rgb, float samples, void* stream);
+int pt_display_apply(pt_display* d, const float* d_rgb, float samples, uint8_t* d_pix,
+                     int32_t pixel_stride, void* stream);
+int pt_display_frame(pt_display* d, const float* d_rgb, float samples, uint8_t* d_pix,
+                     int32_t pixel_stride, void* stream);
+int pt_display_reset(pt_display* d, void* stream);
+/* A host array, synchronous: one object made, used (frame in auto mode, apply otherwise) and destroyed. */
+int pt_display_host(int32_t width, int32_t height, const float* rgb, float samples,
+                    const pt_display_params* p, uint8_t* out, int32_t pixel_stride);
+/* Inspection (synchronous, for tests): the histogram as last resolved (hist[256]: the uncounted pixels),
+ * the exposure state in 1/256 octave, the multiplier apply uses, and whether a metering has set the state
+ * since create or reset.  Any pointer may be NULL. */
+int pt_display_info(pt_display* d, uint32_t hist[257], int32_t* e, float* mult, int32_t* metered);
+/* Host only, no device: the sRGB thresholds T[1..255] (srgb[0] is 0 and not a threshold), P[k] =
+ * (float)exp2(k / 256.0), and the Hable curve's divisor f(11.2f). */
+void pt_display_tables(float srgb[256], float pow2[256], float* hable_white);
+/* The context's accumulated image of `iter` iterations through `d` (metering first in auto mode) into the
+ * caller's device buffer.  d's size must be the tile's and world must be 1 (PT_ERR_ARG otherwise).  Orders
+ * itself like pt_preview_rgba. */
+int pt_preview_display(pt_ctx* c, int32_t iter, pt_display* d, uint8_t* d_pix, int32_t pixel_stride,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
