@@ -11,7 +11,10 @@ from .pathtrace import (  # noqa: F401
     pathtraceInit, render, save_image, save_image_hdr, encode_hdr, tonemap, DenoiseParams, denoise,
     DenoiseVarParams, denoise_variance, TemporalParams, TemporalHistory, AdaptiveParams, JpegParams, JpegEncoder, encode_jpeg,
     PngParams, PngEncoder, encode_png, HdrParams, HdrEncoder, encode_hdr_device, DisplayParams, DisplayTransform,
-    display_transform, display_tables)
+    display_transform, display_tables, ExrParams, ExrChannel, ExrEncoder, encode_exr, exr_ctx_channels)
+from ._native import (  # noqa: F401
+    EXR_UINT, EXR_HALF, EXR_FLOAT, EXR_NONE, EXR_ZIPS, EXR_ZIP, EXR_BEAUTY, EXR_ALBEDO, EXR_NORMAL, EXR_POSITION, EXR_DEPTH,
+    EXR_UV, EXR_ID, EXR_ALL_LAYERS)
 from . import distributed  # noqa: F401
 from .stream_compaction import (CPU, Efficient, Naive, Thrust, compact_device, live_indices_device,  # noqa: F401
                                 naive_scan_device, partition_device, scan_device, thrust_scan_device)
@@ -23,4 +26,6 @@ __all__ = ["Scene", "PathTracer", "GuiDataContainer", "Efficient", "CPU", "Naive
            "InitDataContainer", "DenoiseParams", "denoise", "DenoiseVarParams", "denoise_variance", "TemporalParams",
            "TemporalHistory", "AdaptiveParams", "JpegParams", "JpegEncoder", "encode_jpeg", "PngParams", "PngEncoder", "encode_png",
            "HdrParams", "HdrEncoder", "encode_hdr_device", "DisplayParams", "DisplayTransform", "display_transform",
-           "display_tables", "lib", "LIB_PATH", "NativeLibraryError", "PtError"]
+           "display_tables", "ExrParams", "ExrChannel", "ExrEncoder", "encode_exr", "exr_ctx_channels", "EXR_UINT", "EXR_HALF",
+           "EXR_FLOAT", "EXR_NONE", "EXR_ZIPS", "EXR_ZIP", "EXR_BEAUTY", "EXR_ALBEDO", "EXR_NORMAL", "EXR_POSITION", "EXR_DEPTH",
+           "EXR_UV", "EXR_ID", "EXR_ALL_LAYERS", "lib", "LIB_PATH", "NativeLibraryError", "PtError"]

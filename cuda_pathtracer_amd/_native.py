@@ -168,6 +168,37 @@ class HdrParams(C.Structure):
 assert C.sizeof(HdrParams) == 32
 
 
+class ExrParams(C.Structure):
+    """pt_exr_params; ExrParams.default() = pt_exr_params_default (ZIP, 32 KiB deflate blocks, no mirror)."""
+    _fields_ = [("compression", C.c_int32), ("block_bytes", C.c_int32), ("mirror_x", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+    @classmethod
+    def default(cls) -> "ExrParams":
+        p = cls()
+        lib().pt_exr_params_default(C.byref(p))
+        return p
+
+
+class ExrChannel(C.Structure):
+    """pt_exr_channel: a name of 1 to 31 bytes from [A-Za-z0-9_.] and EXR_UINT, EXR_HALF or EXR_FLOAT."""
+    _fields_ = [("name", C.c_char * 32), ("type", C.c_int32)]
+
+    def __init__(self, name="", type=2):
+        super().__init__((name.encode() if isinstance(name, str) else bytes(name))[:32], int(type))
+
+
+class ExrPlane(C.Structure):
+    """pt_exr_plane: a device pointer, the floats between two pixels and the divisor."""
+    _fields_ = [("d", C.c_void_p), ("stride", C.c_int32), ("divisor", C.c_float)]
+
+
+EXR_UINT, EXR_HALF, EXR_FLOAT = 0, 1, 2   # PT_EXR_* pixel types
+EXR_NONE, EXR_ZIPS, EXR_ZIP = 0, 2, 3     # PT_EXR_* compressions
+EXR_BEAUTY, EXR_ALBEDO, EXR_NORMAL, EXR_POSITION, EXR_DEPTH, EXR_UV, EXR_ID = 1, 2, 4, 8, 16, 32, 64   # PT_EXR_* layers
+EXR_ALL_LAYERS = 127
+assert C.sizeof(ExrParams) == 32 and C.sizeof(ExrChannel) == 36 and C.sizeof(ExrPlane) == 16
+
+
 class DisplayParams(C.Structure):
     """pt_display_params; DisplayParams.default() = pt_display_params_default (manual exposure 1, no curve,
     linear transfer, no mirror: pt_tonemap's conversion)."""
@@ -368,6 +399,18 @@ SIGNATURES = {
     "pt_preview_hdr": (_I, [_P, _I, _P, _P, C.c_int64, _P, _P]),
     "pt_hdr_enc_profile": (_I, [_P, _I]),
     "pt_hdr_enc_profile_read": (_I, [_P, _FP]),
+    "pt_exr_params_default": (None, [C.POINTER(ExrParams)]),
+    "pt_exr_enc_create": (_I, [_I, _I, C.POINTER(ExrChannel), _I, C.POINTER(ExrParams), C.POINTER(_P)]),
+    "pt_exr_enc_destroy": (_I, [_P]),
+    "pt_exr_enc_bound": (C.c_int64, [_P]),
+    "pt_exr_enc_header": (C.c_int64, [_P, _P, C.c_int64]),
+    "pt_exr_enc_planes": (_I, [_P, C.POINTER(ExrPlane), _P, C.c_int64, _P, _P]),
+    "pt_exr_encode_host": (_I, [_I, _I, C.POINTER(ExrChannel), _I, C.POINTER(_P), _IP, _FP, C.POINTER(ExrParams), _P, C.c_int64,
+                                C.POINTER(C.c_int64)]),
+    "pt_exr_enc_profile": (_I, [_P, _I]),
+    "pt_exr_enc_profile_read": (_I, [_P, _FP]),
+    "pt_exr_ctx_channels": (_I, [_I, _I, C.POINTER(ExrChannel), _IP]),
+    "pt_preview_exr": (_I, [_P, _I, _I, _P, _P, C.c_int64, _P, _P]),
     "pt_display_params_default": (None, [C.POINTER(DisplayParams)]),
     "pt_display_create": (_I, [_I, _I, C.POINTER(DisplayParams), C.POINTER(_P)]),
     "pt_display_destroy": (_I, [_P]),
@@ -402,7 +445,7 @@ def _preload_torch() -> None:
 # pt_ctx_exact_counts, pt_selftest_exact: the A/B against the build before the exact tests' single gate;
 # pt_jpeg_*, pt_preview_jpeg: the A/B against the build before the JPEG encoder; pt_png_*, pt_preview_png: the
 # A/B against the build before the PNG encoder; pt_hdr_*, pt_preview_hdr: the A/B against the build before the
-# HDR encoder; pt_display_*, pt_preview_display: scripts/display_time.py's A/B against the build before the display
+# HDR encoder; pt_exr_*, pt_preview_exr: the A/B against the build before the OpenEXR encoder; pt_display_*, pt_preview_display: scripts/display_time.py's A/B against the build before the display
 # transform).
 _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
              "pt_ctx_exact_counts", "pt_selftest_exact",
@@ -425,6 +468,9 @@ _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "p
              "pt_png_enc_accum", "pt_png_encode_host", "pt_preview_png", "pt_png_enc_profile", "pt_png_enc_profile_read",
              "pt_hdr_params_default", "pt_hdr_enc_create", "pt_hdr_enc_destroy", "pt_hdr_enc_bound", "pt_hdr_enc_accum",
              "pt_hdr_encode_host", "pt_preview_hdr", "pt_hdr_enc_profile", "pt_hdr_enc_profile_read",
+             "pt_exr_params_default", "pt_exr_enc_create", "pt_exr_enc_destroy", "pt_exr_enc_bound", "pt_exr_enc_header",
+             "pt_exr_enc_planes", "pt_exr_encode_host", "pt_exr_enc_profile", "pt_exr_enc_profile_read", "pt_exr_ctx_channels",
+             "pt_preview_exr",
              "pt_display_params_default", "pt_display_create", "pt_display_destroy", "pt_display_meter", "pt_display_apply",
              "pt_display_frame", "pt_display_reset", "pt_display_host", "pt_display_info", "pt_display_tables",
              "pt_preview_display"}

@@ -45,6 +45,10 @@ struct CtxHead {
     float* planes = nullptr;
     bool planes_valid = false;
     void release();   // both features off, their state freed (pt_ctx_image.cpp)
+    // pt_preview_exr's first-hit planes gA | gB | alb | uv (14 floats per pixel), from its first call with a layer
+    // other than the beauty until the context is destroyed.
+    float* exr_planes = nullptr;
+    ~CtxHead();       // (pt_ctx_image.cpp)
 };
 
 // Synchronous copy on the context's own non-blocking stream (CtxHead::io_stream): unlike hipMemcpy,

@@ -2,6 +2,7 @@
 // variance tracking, adaptive sampling and temporal frames.  Host code: the kernels it runs are other units',
 // behind their C entry points, and it sees the context through pt_ctx.h (`ctx` the context, `c` its head).
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -19,6 +20,10 @@ void CtxHead::release() {
     mom = nullptr;
     planes = nullptr;
     planes_valid = false;
+}
+
+CtxHead::~CtxHead() {
+    if (exr_planes) (void)hipFree(exr_planes);
 }
 
 int pt::adaptive_apply(pt_ctx* ctx) {
@@ -431,6 +436,65 @@ int pt_preview_png(pt_ctx* ctx, int32_t iter, pt_png_enc* e, uint8_t* d_out, int
 int pt_preview_hdr(pt_ctx* ctx, int32_t iter, pt_hdr_enc* e, uint8_t* d_out, int64_t cap, int64_t* d_size, void* stream) {
     return preview_file(ctx, iter, e, pt_hdr_enc_accum, "HDR", "pt_preview_hdr needs the whole image (world == 1)", d_out, cap,
                         d_size, stream);
+}
+
+// ---- beauty and first-hit layers as OpenEXR -----------------------------------
+// The same ordering.  The beauty planes are the accumulator's, divided by iter in the encoder's convert kernel; the
+// other layers are read in place from pt_gbuffer's planes in the context's scratch.
+int pt_preview_exr(pt_ctx* ctx, int32_t iter, int32_t layers, pt_exr_enc* e, uint8_t* d_out, int64_t cap, int64_t* d_size,
+                   void* stream) {
+    CtxHead* c = ctx_head(ctx);
+    if (!c || !e || !d_out || !d_size || iter <= 0) return pt::fail(PT_ERR_ARG, "bad argument");
+    if (c->world > 1) return pt::fail(PT_ERR_ARG, "pt_preview_exr needs the whole image (world == 1)");
+    int32_t ew = 0, eh = 0;
+    pt::enc_size(pt::enc_head(e), &ew, &eh);
+    if (ew != c->W || (int64_t)ew * eh != (int64_t)c->npix)
+        return pt::fail(PT_ERR_ARG, "the EXR encoder and the context's tile differ in size");
+    // the encoder's channels: pt_exr_ctx_channels(layers, half)'s, with `half` read off the first channel of each layer
+    const pt_exr_channel* have = nullptr;
+    int32_t nhave = 0, nwant = 0, half = 0;
+    pt::exr_channels(e, &have, &nhave);
+    pt_exr_channel want[16];
+    if (int rc = pt_exr_ctx_channels(layers, 0, want, &nwant)) return rc;
+    bool same = nhave == nwant;
+    if (same) {
+        int at = 0;
+        for (int32_t bit = 1; bit <= PT_EXR_ID; bit <<= 1) {
+            if (!(layers & bit)) continue;
+            if (have[at].type == PT_EXR_HALF) half |= bit;
+            at += bit == PT_EXR_DEPTH || bit == PT_EXR_ID ? 1 : (bit == PT_EXR_UV ? 2 : 3);
+        }
+        (void)pt_exr_ctx_channels(layers, half, want, &nwant);
+        for (int k = 0; k < nwant; ++k) same = same && !std::strcmp(have[k].name, want[k].name) && have[k].type == want[k].type;
+    }
+    if (!same) return pt::fail(PT_ERR_ARG, "the EXR encoder's channels are not pt_exr_ctx_channels' for these layers");
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t n = c->npix;
+    if ((layers & ~PT_EXR_BEAUTY) && !c->exr_planes && hipMalloc((void**)&c->exr_planes, n * 14 * sizeof(float)) != hipSuccess) {
+        c->exr_planes = nullptr;
+        (void)hipGetLastError();
+        return pt::fail(PT_ERR_NOMEM, "hipMalloc (EXR layers)");
+    }
+    float* s = c->exr_planes;
+    if (layers & ~PT_EXR_BEAUTY) {
+        if (int rc = pt_gbuffer(ctx, s, s + 4 * n, s + 8 * n, s + 12 * n, st)) return rc;   // (waits for the finalize, marks the context)
+    } else if (int rc = wait_finalize(c, st)) {
+        return rc;
+    }
+    pt_exr_plane pl[16];
+    int at = 0;
+    auto add = [&](const float* d, int count, int stride, float divisor) {
+        for (int k = 0; k < count; ++k) pl[at++] = pt_exr_plane{d + k, stride, divisor};
+    };
+    if (layers & PT_EXR_BEAUTY) add(c->image, 3, 3, (float)iter);
+    if (layers & PT_EXR_ALBEDO) add(s + 8 * n, 3, 4, 1.0f);
+    if (layers & PT_EXR_NORMAL) add(s, 3, 4, 1.0f);
+    if (layers & PT_EXR_POSITION) add(s + 4 * n, 3, 4, 1.0f);
+    if (layers & PT_EXR_DEPTH) add(s + 4 * n + 3, 1, 4, 1.0f);
+    if (layers & PT_EXR_UV) add(s + 12 * n, 2, 2, 1.0f);
+    if (layers & PT_EXR_ID) add(s + 3, 1, 4, 1.0f);
+    if (int rc = pt_exr_enc_planes(e, pl, d_out, cap, d_size, st)) return rc;
+    return mark_ctx(c, st);
 }
 
 // ---- display bytes ------------------------------------------------------------

@@ -74,7 +74,10 @@ struct EncHead;
 const EncHead* enc_head(const pt_jpeg_enc* e);
 const EncHead* enc_head(const pt_png_enc* e);
 const EncHead* enc_head(const pt_hdr_enc* e);
+const EncHead* enc_head(const pt_exr_enc* e);
 void enc_size(const EncHead* e, int32_t* width, int32_t* height);
+// pt_exr_enc (pt_exr_enc.hip): the channels it was created with, in creation order (e not null)
+void exr_channels(const pt_exr_enc* e, const pt_exr_channel** channels, int32_t* n);
 // pt_display (pt_display.hip): the image size it was created for and whether its exposure is metered
 int display_size(const pt_display* d, int32_t* width, int32_t* height, int32_t* automatic);
 

@@ -5,7 +5,10 @@
 //
 //   pathtracer_amd SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise]
 //                  [--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png]
-//                  [--device-hdr] [--tonemap none|reinhard|aces|hable] [--exposure EV|auto] [--srgb]
+//                  [--device-hdr] [--tonemap none|reinhard|aces|hable] [--exposure EV|auto] [--srgb] [--exr] [--exr-half]
+// --exr additionally writes ...samp.exr, an OpenEXR file written on the device (pt_preview_exr, DESIGN.md §18: FLOAT, ZIP,
+// x-mirrored like every saved image) with the beauty layer R, G, B and, with --aov DIR, the six first-hit layers beside
+// it in the same file; --exr-half stores the layers that may be HALF as HALF.  The other files keep their names and bytes.
 // --tonemap, --exposure, --srgb: any of them additionally writes ...samp.display.png, the accumulator through the
 // display transform (pt_preview_display, DESIGN.md §17: the tone curve, an exposure of EV stops or a metered one,
 // the sRGB transfer), x-mirrored like every saved image and written by the device PNG encoder from the device
@@ -128,6 +131,28 @@ std::string saveHdrDevice(const Scene& scene, const std::string& dir, const std:
         return pt_preview_hdr(pathtraceContext(), iteration, enc, d_out, cap, d_size, nullptr);
     });
     pt_hdr_enc_destroy(enc);
+    return filename;
+}
+
+// --exr: ...samp.exr, the layers `layers` (HALF for those of `half` that may be) in one OpenEXR file written on the device.
+std::string saveExrDevice(const Scene& scene, const std::string& dir, const std::string& start, int iteration, int32_t layers,
+                          int32_t half) {
+    pt_exr_params prm;
+    pt_exr_params_default(&prm);
+    prm.mirror_x = 1;
+    pt_exr_channel channels[16];
+    int32_t n = 0;
+    pt_exr_enc* enc = nullptr;
+    if (pt_exr_ctx_channels(layers, half, channels, &n) ||
+        pt_exr_enc_create(scene.state.camera.res[0], scene.state.camera.res[1], channels, n, &prm, &enc)) {
+        std::fprintf(stderr, "saveImage (device): encoder: %s\n", pt_last_error());
+        std::exit(EXIT_FAILURE);
+    }
+    const std::string filename = saveDeviceFile(scene, dir, start, iteration, ".exr", pt_exr_enc_bound(enc),
+                                                [&](uint8_t* d_out, int64_t cap, int64_t* d_size) {
+        return pt_preview_exr(pathtraceContext(), iteration, layers, enc, d_out, cap, d_size, nullptr);
+    });
+    pt_exr_enc_destroy(enc);
     return filename;
 }
 
@@ -267,14 +292,14 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::printf("Usage: %s SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise] "
                     "[--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png] [--device-hdr] "
-                    "[--tonemap none|reinhard|aces|hable] [--exposure EV|auto] [--srgb]\n", argv[0]);
+                    "[--tonemap none|reinhard|aces|hable] [--exposure EV|auto] [--srgb] [--exr] [--exr-half]\n", argv[0]);
         return 1;
     }
     const char* sceneFile = argv[1];
     int iterations = -1;
     std::string out_dir, aov_dir;
     bool sort = false, png = true, hdr = false, denoise = false, denoise_var = false, aov = false, adaptive = false;
-    bool device_png = false, device_hdr = false;
+    bool device_png = false, device_hdr = false, exr = false, exr_half = false;
     float adaptive_threshold = 0.0f;
     int adaptive_every = 4;
     bool display = false;
@@ -289,6 +314,8 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--device-png")) device_png = true;
         else if (!std::strcmp(argv[i], "--device-hdr")) device_hdr = true;
         else if (!std::strcmp(argv[i], "--hdr")) hdr = true;   // also write the saveHDR .hdr file
+        else if (!std::strcmp(argv[i], "--exr")) exr = true;
+        else if (!std::strcmp(argv[i], "--exr-half")) exr_half = true;
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
         else if (!std::strcmp(argv[i], "--denoise-variance")) denoise_var = true;
         else if (!std::strcmp(argv[i], "--aov") && i + 1 < argc) { aov_dir = argv[++i]; aov = true; }
@@ -365,6 +392,9 @@ int main(int argc, char** argv) {
         std::printf("wrote %s\n", device_hdr ? saveHdrDevice(*scene, out_dir, startTimeString, iteration).c_str()
                                              : saveImage(*scene, out_dir, startTimeString, iteration, true).c_str());
     if (display) std::printf("wrote %s\n", saveDisplayDevice(*scene, out_dir, startTimeString, iteration, dprm).c_str());
+    if (exr)
+        std::printf("wrote %s\n", saveExrDevice(*scene, out_dir, startTimeString, iteration, aov ? PT_EXR_ALL_LAYERS : PT_EXR_BEAUTY,
+                                                exr_half ? PT_EXR_ALL_LAYERS : 0).c_str());
     if (denoise) {
         std::vector<float> dn((size_t)scene->state.camera.res[0] * scene->state.camera.res[1] * 3);
         pt_denoise_params prm;

@@ -20,8 +20,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, DisplayParams, HdrParams, JpegParams, PngParams,  # noqa: F401
-                      TemporalParams, check_pt, lib)
+from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, DisplayParams, ExrChannel, ExrParams, HdrParams,  # noqa: F401
+                      JpegParams, PngParams, TemporalParams, check_pt, lib)
 
 SPHERE, CUBE, MESH = 0, 1, 2
 
@@ -488,6 +488,29 @@ class PathTracer:
             f.write(data)
         return str(path)
 
+    def preview_exr(self, iteration: int, encoder: "ExrEncoder", layers: int = N.EXR_BEAUTY, stream=None) -> bytes:
+        """The layers `layers` (a mask of EXR_BEAUTY .. EXR_ID) as one OpenEXR file written on the device by `encoder`
+        (pt_preview_exr), whose channels must be exr_ctx_channels(layers, half)'s: the accumulated image of `iteration`
+        iterations and the first-hit planes.  Only the file crosses to the host."""
+        out, size = encoder._buffers()
+        check_pt(lib().pt_preview_exr(self._h, int(iteration), int(layers), encoder._h, out.data_ptr(), encoder.cap,
+                                      size.data_ptr(), _stream_ptr(stream)))
+        return encoder._read(stream)
+
+    def save_exr(self, path: str, iteration: int, layers: int = N.EXR_BEAUTY, half: int = 0) -> str:
+        """The layers as a ZIP-compressed OpenEXR file, x-mirrored like every saved image, written on the device; the
+        layers of `half` that may be are stored as HALF."""
+        prm = N.ExrParams.default()
+        prm.mirror_x = 1
+        enc = ExrEncoder(self.width, self.rows, exr_ctx_channels(layers, half), prm)
+        try:
+            data = self.preview_exr(iteration, enc, layers)
+        finally:
+            enc.free()
+        with open(path, "wb") as f:
+            f.write(data)
+        return str(path)
+
     def gbuffer(self) -> dict:
         """First-hit feature planes of the tile (pt_get_gbuffer; the deterministic camera ray): normal
         (rows, W, 3), mat (rows, W) int32 with -1 on a miss, position (rows, W, 3), t (rows, W) with -1
@@ -896,6 +919,107 @@ def encode_jpeg(rgb8: np.ndarray, quality: int = 90, subsampling="420", mirror_x
     per = 3 if m == 8 else 6   # blocks of an MCU; pt_jpeg_enc_bound: 208 bytes a block, twice when stuffed
     return _encode_host(lib().pt_jpeg_encode_host, rgb8, prm,
                         lambda w, h: 623 + 2 * (per * ((w + m - 1) // m) * ((h + m - 1) // m) * 208) + 2)
+
+
+def _exr_channels(channels) -> "C.Array":
+    """A ctypes array of pt_exr_channel from ExrChannel objects or (name, type) pairs."""
+    items = [c if isinstance(c, N.ExrChannel) else N.ExrChannel(*c) for c in channels]
+    return (N.ExrChannel * max(len(items), 1))(*items)
+
+
+class ExrEncoder(_Encoder):
+    """pt_exr_enc: an OpenEXR encoder on the device for `channels` (ExrChannel objects or (name, type)
+    pairs, in any order; an encode takes its planes in this order); params: an ExrParams (default: ZIP, no mirror).
+    Its source is a list of float planes."""
+
+    _format, _params = "EXR", N.ExrParams
+
+    def __init__(self, width: int, height: int, channels, params=None, cap: int | None = None):
+        self.width, self.height = int(width), int(height)
+        self._h = C.c_void_p()
+        self._out = self._size = self._pix = None
+        L = lib()
+        self._destroy = L.pt_exr_enc_destroy
+        self.channels = list(channels)
+        prm = params if params is not None else N.ExrParams.default()
+        check_pt(L.pt_exr_enc_create(self.width, self.height, _exr_channels(self.channels), len(self.channels), C.byref(prm),
+                                     C.byref(self._h)))
+        self.bound = int(L.pt_exr_enc_bound(self._h))
+        self.cap = self.bound if cap is None else int(cap)
+
+    def header(self) -> bytes:
+        """The file from its magic number through the header's final zero byte (pt_exr_enc_header; no device needed)."""
+        n = int(lib().pt_exr_enc_header(self._h, None, 0))
+        buf = (C.c_uint8 * n)()
+        lib().pt_exr_enc_header(self._h, buf, n)
+        return bytes(buf)
+
+    def encode(self, planes, strides=None, divisors=None, stream=None) -> bytes:
+        """One file.  planes: per channel, in creation order, an array or tensor of 4-byte elements (float32, or
+        uint32 / int32 for a UINT channel) that holds the pixel p at element p * stride, or a device pointer (int) to
+        one; the same object may be given for several channels.  strides, divisors: per channel, default 1."""
+        import torch
+        n = len(self.channels)
+        if len(planes) != n:
+            raise ValueError(f"{len(planes)} planes for {n} channels")
+        strides = [1] * n if strides is None else [int(s) for s in strides]
+        divisors = [1.0] * n if divisors is None else [float(d) for d in divisors]
+        keep, arr = {}, (N.ExrPlane * n)()
+        for k, src in enumerate(planes):
+            if isinstance(src, int):
+                ptr = src
+            else:
+                if id(src) not in keep:
+                    if not isinstance(src, torch.Tensor) and np.asarray(src).dtype.itemsize != 4:
+                        raise ValueError(f"plane {k}: {np.asarray(src).dtype}, expected 4-byte elements")
+                    t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src).view(np.int32))
+                    need = (self.width * self.height - 1) * strides[k] + 1
+                    if t.element_size() != 4 or t.numel() < need:
+                        raise ValueError(f"plane {k}: {tuple(t.shape)} {t.dtype}, expected at least {need} 4-byte elements")
+                    keep[id(src)] = t.contiguous().cuda()
+                ptr = keep[id(src)].data_ptr()
+            arr[k] = N.ExrPlane(ptr, strides[k], divisors[k])
+        out, size = self._buffers()
+        check_pt(lib().pt_exr_enc_planes(self._h, arr, out.data_ptr(), self.cap, size.data_ptr(), _stream_ptr(stream)))
+        data = self._read(stream)
+        del keep
+        return data
+
+
+_EXR_COMPRESSION = {"none": N.EXR_NONE, "zips": N.EXR_ZIPS, "zip": N.EXR_ZIP}
+
+
+def encode_exr(channels: dict, half=(), compression="zip", mirror_x: bool = False) -> bytes:
+    """{name: (H, W) float32 or uint32 array} as an OpenEXR file written on the device (pt_exr_encode_host): a float32
+    array is a FLOAT channel, or HALF when its name is in `half`; a uint32 (or int32) array is a UINT channel."""
+    names = list(channels)
+    arrs = [np.ascontiguousarray(channels[k]) for k in names]
+    if not arrs or any(a.ndim != 2 or a.shape != arrs[0].shape or a.dtype.itemsize != 4 for a in arrs):
+        raise ValueError("encode_exr: (H, W) arrays of one shape, float32 or uint32")
+    h, w = arrs[0].shape
+    types = [N.EXR_UINT if a.dtype.kind in "ui" else (N.EXR_HALF if k in half else N.EXR_FLOAT) for k, a in zip(names, arrs)]
+    prm = N.ExrParams.default()
+    comp = _EXR_COMPRESSION.get(compression, compression)
+    if comp not in _EXR_COMPRESSION.values():
+        raise ValueError(f"compression {compression!r}: 'none', 'zips' or 'zip'")
+    prm.compression, prm.mirror_x = comp, int(bool(mirror_x))
+    chans = _exr_channels(list(zip(names, types)))
+    ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    nchunks = -(-h // (16 if comp == N.EXR_ZIP else 1))
+    # pt_exr_enc_bound, with room for the largest header
+    out = np.empty(1280 + 16 * nchunks + h * w * sum(2 if t == N.EXR_HALF else 4 for t in types), np.uint8)
+    n = C.c_int64(0)
+    check_pt(lib().pt_exr_encode_host(w, h, chans, len(arrs), ptrs, None, None, C.byref(prm), out.ctypes.data, out.size,
+                                      C.byref(n)))
+    return out[:n.value].tobytes()
+
+
+def exr_ctx_channels(layers: int, half: int = 0) -> list:
+    """pt_exr_ctx_channels: the (name, type) pairs of a render context's `layers` (a mask of EXR_BEAUTY .. EXR_ID), HALF
+    for the layers of `half` that may be."""
+    out, n = (N.ExrChannel * 16)(), C.c_int32(0)
+    check_pt(lib().pt_exr_ctx_channels(int(layers), int(half), out, C.byref(n)))
+    return [(out[k].name.decode(), int(out[k].type)) for k in range(n.value)]
 
 
 def _png_params(filter=None, block_bytes: int | None = None, conv: int | None = None, mirror_x: bool = False) -> "N.PngParams":

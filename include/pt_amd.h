@@ -774,6 +774,93 @@ int pt_preview_hdr(pt_ctx* c, int32_t iter, pt_hdr_enc* e, uint8_t* d_out, int64
 int pt_hdr_enc_profile(pt_hdr_enc* e, int32_t on);
 int pt_hdr_enc_profile_read(pt_hdr_enc* e, float ms[4]);
 
+/* ---- OpenEXR encoding on the device ------------------------------------------- */
+/* A single-part scanline OpenEXR 2.0 file of width x height pixels and 1 to 16 channels, written entirely by
+ * kernels from float planes in device memory: uncompressed, or ZIPS / ZIP (one zlib stream per 1 / 16 scanlines
+ * over the byte-split, differenced chunk, coded by §15's run-length deflate; the chunk's raw bytes where the
+ * stream would not be shorter).  DESIGN.md §18 defines every byte of the file.  The value of channel k at a pixel
+ * is plane_k.d[pixel * stride] / divisor (one float32 division; a divisor of 1 is the identity), `pixel` in
+ * pt_get_image's order; FLOAT stores its bits, HALF the IEEE round-to-nearest-even half (subnormals kept, overflow
+ * to infinity, NaN as sign | 0x7e00), UINT the plane word's 32 bits unchanged (the divisor is ignored).
+ * mirror_x reads column W-1-x.  The object needs no context; pt_exr_enc_create touches no device (argument
+ * errors, PT_ERR_ARG, are found before any device call) and the scratch is allocated at the first encode; later
+ * encodes neither allocate nor synchronise.  Sizes whose bound reaches 2^31, or whose stream bound
+ * 16 + 9 n + 10 blocks bits (n the bytes of 1 / 16 scanlines) does, are refused. */
+#define PT_EXR_UINT 0
+#define PT_EXR_HALF 1
+#define PT_EXR_FLOAT 2
+#define PT_EXR_NONE 0
+#define PT_EXR_ZIPS 2 /* one zlib stream per scanline */
+#define PT_EXR_ZIP 3  /* one per 16 scanlines */
+typedef struct pt_exr_params {
+    int32_t compression;  /* default PT_EXR_ZIP */
+    int32_t block_bytes;  /* bytes of a stream per deflate block: a multiple of 512 in 1024..1048576, default 32768 */
+    int32_t mirror_x;     /* default 0 */
+    int32_t reserved[5];
+} pt_exr_params;
+void pt_exr_params_default(pt_exr_params* p);
+typedef struct pt_exr_channel {
+    char name[32];        /* 1 to 31 bytes of [A-Za-z0-9_.], zero-terminated; distinct within a file */
+    int32_t type;         /* PT_EXR_UINT, PT_EXR_HALF or PT_EXR_FLOAT */
+} pt_exr_channel;
+typedef struct pt_exr_plane {
+    const float* d;       /* device memory; planes may alias each other, none may overlap the output */
+    int32_t stride;       /* floats between two pixels, >= 1 */
+    float divisor;        /* finite, > 0 */
+} pt_exr_plane;
+typedef struct pt_exr_enc pt_exr_enc;
+/* The channels in any order: the file lists them sorted by the bytes of their names, and an encode takes its
+ * planes in the order given here. */
+int pt_exr_enc_create(int32_t width, int32_t height, const pt_exr_channel* channels, int32_t nchannels,
+                      const pt_exr_params* p, pt_exr_enc** out);
+int pt_exr_enc_destroy(pt_exr_enc* e);
+/* The uncompressed file's size, header + 8 chunks + the sum over the chunks of (8 + n): the raw fallback makes it
+ * a bound for every compression.  No device. */
+int64_t pt_exr_enc_bound(const pt_exr_enc* e);
+/* The file from its magic number through the header's final zero byte, to buf (at most cap bytes; NULL: the
+ * length only); returns the length.  No device. */
+int64_t pt_exr_enc_header(const pt_exr_enc* e, uint8_t* buf, int64_t cap);
+/* Asynchronous on `stream`, device pointers (the caller orders the calls of one object): one plane per channel.
+ * The file goes to d_out and its size to *d_size (8-byte aligned); a file that does not fit cap leaves the
+ * negated size it needs in *d_size, and no byte at or beyond d_out + cap is written. */
+int pt_exr_enc_planes(pt_exr_enc* e, const pt_exr_plane* planes, uint8_t* d_out, int64_t cap, int64_t* d_size,
+                      void* stream);
+/* Host arrays, synchronous: plane k holds width * height * strides[k] floats (strides NULL: all 1; divisors
+ * NULL: all 1).  A file larger than cap: PT_ERR_ARG, the size it needs in *size. */
+int pt_exr_encode_host(int32_t width, int32_t height, const pt_exr_channel* channels, int32_t nchannels,
+                       const float* const* planes, const int32_t* strides, const float* divisors,
+                       const pt_exr_params* p, uint8_t* out, int64_t cap, int64_t* size);
+/* Stage timing of an encoder: while on, an encode records events around its stages; read waits for the last
+ * encode and returns the milliseconds of convert and difference, block codes and count, the per-stream scan, zero
+ * and emit, checksums and chunk sizes, and the output copy with the table and header. */
+int pt_exr_enc_profile(pt_exr_enc* e, int32_t on);
+int pt_exr_enc_profile_read(pt_exr_enc* e, float ms[6]);
+/* The layers a render context can write, and their channels:
+ *   PT_EXR_BEAUTY    R, G, B                        the accumulator / iter
+ *   PT_EXR_ALBEDO    albedo.R, albedo.G, albedo.B   pt_gbuffer's alb
+ *   PT_EXR_NORMAL    N.X, N.Y, N.Z                  gA
+ *   PT_EXR_POSITION  P.X, P.Y, P.Z                  gB, always FLOAT
+ *   PT_EXR_DEPTH     Z                              gB's t (-1 on a miss), always FLOAT
+ *   PT_EXR_UV        UV.U, UV.V                     uv
+ *   PT_EXR_ID        id                             gA's material id bits, UINT
+ * pt_exr_ctx_channels lists the channels of `layers` (a non-empty mask) in this order, FLOAT, or HALF for the
+ * layers of `half` that may be HALF (the other bits of `half` are ignored).  No device. */
+#define PT_EXR_BEAUTY 1
+#define PT_EXR_ALBEDO 2
+#define PT_EXR_NORMAL 4
+#define PT_EXR_POSITION 8
+#define PT_EXR_DEPTH 16
+#define PT_EXR_UV 32
+#define PT_EXR_ID 64
+#define PT_EXR_ALL_LAYERS 127
+int pt_exr_ctx_channels(int32_t layers, int32_t half, pt_exr_channel out[16], int32_t* n);
+/* The context's layers encoded by `e`, whose size must be the tile's and whose channels must be
+ * pt_exr_ctx_channels(layers, half)'s for some `half` (PT_ERR_ARG otherwise; a sharded context, world > 1, is
+ * refused).  Layers other than the beauty come from pt_gbuffer into a scratch of 14 floats per pixel that the
+ * context keeps until pt_destroy.  Orders itself like pt_preview_rgba. */
+int pt_preview_exr(pt_ctx* c, int32_t iter, int32_t layers, pt_exr_enc* e, uint8_t* d_out, int64_t cap,
+                   int64_t* d_size, void* stream);
+
 /* ---- display transform on the device ------------------------------------------ */
 /* The float accumulator to display bytes (RGB8 or RGBA8 with alpha 0): an exposure multiplier, manual or
  * metered from a luminance histogram, a tone curve, the clamp to 0..1 and a transfer function.  The bytes
