@@ -73,6 +73,22 @@ class Stats(C.Structure):
                 ("bound_mismatch", C.c_uint32)]
 
 
+class BoundInfo(C.Structure):
+    """pt_bound_info: one geom's row of pt_scene_bound_info."""
+    _fields_ = [("bkind", C.c_int32), ("slo", C.c_float * 3), ("shi", C.c_float * 3), ("wlo", C.c_float * 3),
+                ("whi", C.c_float * 3), ("tight", C.c_float * 6), ("tslack", C.c_float), ("back", C.c_float),
+                ("wback", C.c_float)]
+
+
+class BoundsReport(C.Structure):
+    """pt_bounds_report: what pt_selftest_bounds counts."""
+    _fields_ = [("pairs", C.c_uint64 * 5), ("bad_tagged", C.c_uint64 * 5), ("bad_float", C.c_uint64 * 5),
+                ("rays", C.c_uint64 * 6), ("skipped", C.c_uint64 * 6), ("has_first", C.c_uint32),
+                ("first_geom", C.c_uint32), ("first_form", C.c_uint32), ("first_origin", C.c_uint32 * 3),
+                ("first_dir", C.c_uint32 * 3), ("first_bound", C.c_uint32), ("first_t", C.c_uint32),
+                ("pad_", C.c_uint32)]
+
+
 class DenoiseParams(C.Structure):
     """pt_denoise_params; DenoiseParams.default() = pt_denoise_params_default."""
     _fields_ = [("levels", C.c_int32), ("sigma_c", C.c_float), ("sigma_n", C.c_float), ("sigma_p", C.c_float),
@@ -281,6 +297,8 @@ SIGNATURES = {
     "pt_scene_bvh_quads": (_I, [_P, _P, _I, _IP, _IP]),
     "pt_scene_bvh_tcull": (_I, [_P, C.POINTER(C.c_uint32), _I, C.POINTER(C.c_double)]),
     "pt_scene_room_info": (_I, [_P, C.POINTER(Flags), _IP, _IP, _FP, _FP]),
+    "pt_scene_bound_info": (_I, [_P, C.POINTER(Flags), C.POINTER(BoundInfo), _I, C.POINTER(C.c_double),
+                                 C.POINTER(C.c_double), _IP, _FP, _FP]),
     "pt_create": (_I, [_P, C.POINTER(Flags), C.POINTER(Shard), C.POINTER(_P)]),
     "pt_destroy": (_I, [_P]),
     "pt_set_flags": (_I, [_P, C.POINTER(Flags)]),
@@ -308,6 +326,7 @@ SIGNATURES = {
     "pt_profile_enable": (_I, [_P, _I]),
     "pt_selftest_math": (_I, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     "pt_selftest_exact": (_I, [C.c_uint64, C.c_uint32] + [C.POINTER(C.c_uint64)] * 3),
+    "pt_selftest_bounds": (_I, [_P, C.POINTER(Flags), C.c_uint64, C.c_uint32, C.POINTER(BoundsReport)]),
     "pt_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "pt_profile_read_busy": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "pt_profile_read_kinds": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
@@ -443,12 +462,13 @@ def _preload_torch() -> None:
 # variance entry points, pt_temporal_* and pt_adaptive_*: the A/B against the builds before them;
 # pt_ctx_depart_counts: the A/B against the build before the room's departure claim;
 # pt_ctx_exact_counts, pt_selftest_exact: the A/B against the build before the exact tests' single gate;
+# pt_scene_bound_info, pt_selftest_bounds: the A/B against the build before the per-pair bound check;
 # pt_jpeg_*, pt_preview_jpeg: the A/B against the build before the JPEG encoder; pt_png_*, pt_preview_png: the
 # A/B against the build before the PNG encoder; pt_hdr_*, pt_preview_hdr: the A/B against the build before the
 # HDR encoder; pt_exr_*, pt_preview_exr: the A/B against the build before the OpenEXR encoder; pt_display_*, pt_preview_display: scripts/display_time.py's A/B against the build before the display
 # transform).
 _OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
-             "pt_ctx_exact_counts", "pt_selftest_exact",
+             "pt_ctx_exact_counts", "pt_selftest_exact", "pt_scene_bound_info", "pt_selftest_bounds",
              "pt_moments_create",
              "pt_moments_destroy", "pt_moments_reset", "pt_moments_update", "pt_moments_info", "pt_moments_variance",
              "pt_moments_get", "pt_denoise_var_params_default", "pt_denoiser_run_var", "pt_denoise_var_host",

@@ -153,7 +153,7 @@ void find_room(BoundsHost& B) {
     }
     const std::vector<DGeom>& G = B.geoms;
     const size_t n = G.size();
-    if (n > (size_t)kLdsGeoms) return;
+    if (n > (size_t)kLdsGeoms || B.unbounded) return;
     if (const char* e = std::getenv("PT_AMD_ROOM"))
         if (std::atoi(e) == 0) return;
     // the cubes' own (unwidened) world boxes
@@ -248,9 +248,85 @@ void find_room(BoundsHost& B) {
 // mu_a = 2^-18 (S_a + 1) is >= 10x that.  The sphere's b^2 - a c cancels to <= 2^-20 (S + 1)^2:
 // kappa = 2^-16 (S + 1)^2.  tslack covers the back-transform (transform * inverse != I in float)
 // and the rounding of the reference's length(); abs_slack its absolute part.
+//   The range of the forms.  With |ro|_inf <= R and |rd| < 2 the largest finite intermediates are the
+// spheres' (bound_geom<2>, <4>, bound_sphere_tagged): |qo_a| <= S_a and |qv_a| <= 2 cs_a give
+// q2 <= 3 S^2, |b| <= 6 S cs and a <= 12 cs^2, so b * b and a * (q2 - r2w) stay below
+// 36 S^2 cs^2 + 12 cs^2 r2w < 40 (S + 1)^2 (cs + 1)^2 each and their difference below twice that; the
+// departing test's (q2 + 1) * (kcs * rinf + kc3) stays below (3 S^2 + 1) 2^-17 (S + 2) < 2^-15 (S + 2)^3;
+// bkind 4 takes the dot products in world space first, dot(w, w) <= 12 R^2.  The cubes' forms multiply
+// a difference of at most 2 S + 1 (object slabs) or 2 R (1 + 2^-17) (world planes) by a reciprocal of a
+// direction component, which is infinite for an axis-parallel ray by design (the slab parameters then
+// order as the reference's do), so their only condition is that the differences themselves, and the
+// host's constants (mu, the pads, abs_slack), are finite floats.  If a sphere's b * b and a * q2 both
+// overflow, disc = inf - inf is a NaN, the tagged form calls a sphere the ray hits a miss, and the
+// closest hit is wrong.  bound_range is the largest of these magnitudes at a given R; the scene is
+// bounded while it stays within kBoundRange = 2^126, one binade below the first float that rounds to
+// infinity, and BoundsHost::r_limit is the R at which it gets there (bisected: every term grows with R).
+//   Beyond r_limit the context keeps its kernels and gives every cube and sphere the one bound that
+// claims nothing: bkind 3 with an infinite world box, back = wback = 0, tslack = 1, abs_slack = 0 and no
+// room.  bound_wbox_tagged then returns E0 = 0, X = +inf, the tag of +0 for every ray (a finite origin
+// minus an infinite plane is infinite, times a nonzero or infinite reciprocal still infinite, and never
+// NaN), so pass 2 runs the exact test of every geom for every ray: the reference's loop.
+constexpr double kBoundRange = 0x1p126;
+static double bound_range(const BoundsHost& B, double R) {
+    double m = 4.0 * (R + 1.0);
+    for (const DGeom& d : B.geoms) {
+        if (d.type != PT_GEOM_CUBE && d.type != PT_GEOM_SPHERE) continue;
+        double smax = 0.0, cs = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            double S = std::fabs((double)d.inv.c[3][a]), c = 0.0;
+            for (int i = 0; i < 3; ++i) {
+                S += std::fabs((double)d.inv.c[i][a]) * R;
+                c += std::fabs((double)d.inv.c[i][a]);
+            }
+            smax = std::max(smax, S);
+            cs = std::max(cs, c);
+        }
+        m = std::max(m, 4.0 * (smax + 1.0));
+        if (d.type == PT_GEOM_SPHERE) {
+            m = std::max(m, 80.0 * (smax + 1.0) * (smax + 1.0) * (cs + 1.0) * (cs + 1.0));
+            m = std::max(m, std::ldexp((smax + 2.0) * (smax + 2.0) * (smax + 2.0), -15));
+            m = std::max(m, 16.0 * (R + 1.0) * (R + 1.0));
+        }
+    }
+    return m;   // (+inf or NaN for entries beyond double's own range: not within any limit)
+}
+static double bound_r_limit(const BoundsHost& B) {
+    if (!(bound_range(B, 0.0) <= kBoundRange)) return 0.0;
+    double lo = 0.0, hi = 0x1p127;
+    for (int it = 0; it < 200; ++it) {
+        const double mid = lo == 0.0 ? hi * 0x1p-8 : std::sqrt(lo * hi);
+        if (mid == lo || mid == hi) break;
+        if (bound_range(B, mid) <= kBoundRange) lo = mid;
+        else hi = mid;
+        if (lo == 0.0 && hi < 0x1p-1000) break;
+    }
+    return lo;
+}
+
 void update_bounds(BoundsHost& B, float aperture) {
     const double R = B.scene_ext + std::fabs((double)aperture) + 1e-2;
+    B.R = R;
+    B.r_limit = bound_r_limit(B);
+    B.unbounded = !(R <= B.r_limit);
     B.wtight.assign(6 * B.geoms.size(), 0.0f);
+    if (B.unbounded) {
+        for (DGeom& d : B.geoms) {
+            d.bkind = (d.type == PT_GEOM_CUBE || d.type == PT_GEOM_SPHERE) ? 3 : 0;
+            for (int k = 0; k < 3; ++k) {
+                d.slo[k] = d.wlo[k] = d.wbox[2 * k] = -HUGE_VALF;
+                d.shi[k] = d.whi[k] = d.wbox[2 * k + 1] = HUGE_VALF;
+            }
+            d.r2w = HUGE_VALF;
+            d.kcs = d.kc3 = 0.0f;
+            d.tslack = 1.0f;
+            d.back = d.wback = 0.0f;
+        }
+        B.abs_slack = 0.0f;
+        B.wb_tslack = 1.0f;
+        find_room(B);   // (no room: unbounded)
+        return;
+    }
     for (DGeom& d : B.geoms) {
         double smax = 0.0;
         for (int a = 0; a < 3; ++a) {
@@ -459,7 +535,7 @@ void camera_masks(const BoundsHost& B, const CamDev& cam, const FlagsDev& fl, co
     std::vector<bool> always((size_t)ng, false);
     for (int g = 0; g < ng; ++g) {
         const DGeom& d = B.geoms[(size_t)g];
-        if (d.type != PT_GEOM_CUBE && d.type != PT_GEOM_SPHERE) { always[(size_t)g] = true; continue; }
+        if ((d.type != PT_GEOM_CUBE && d.type != PT_GEOM_SPHERE) || B.unbounded) { always[(size_t)g] = true; continue; }
         double X[3][3];
         const double det = invert_linear(d.inv, X);
         if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) { always[(size_t)g] = true; continue; }
@@ -570,5 +646,38 @@ extern "C" int pt_scene_room_info(const pt_scene* scene, const pt_flags* flags, 
     pt::BoundsHost B = pt::make_dgeoms(S);
     pt::update_bounds(B, f.aperture);
     pt::room_info(B.room, walls, faces, lo, hi);
+    return PT_OK;
+}
+
+extern "C" int pt_scene_bound_info(const pt_scene* scene, const pt_flags* flags, pt_bound_info* rows, int32_t cap,
+                                   double* R, double* r_limit, int32_t* bounded, float* abs_slack, float* wb_tslack) {
+    if (!scene || (cap > 0 && !rows)) return pt::fail(PT_ERR_ARG, "null argument");
+    const auto& S = *reinterpret_cast<const pt::Scene*>(scene);
+    if (!S.finalized) return pt::fail(PT_ERR_ARG, "scene not finalized (pt_scene_finalize)");
+    pt_flags f;
+    if (flags) f = *flags;
+    else pt_flags_default(&f);
+    pt::BoundsHost B = pt::make_dgeoms(S);
+    pt::update_bounds(B, f.aperture);
+    for (size_t i = 0; i < B.geoms.size() && (int64_t)i < (int64_t)cap; ++i) {
+        const ptd::DGeom& d = B.geoms[i];
+        pt_bound_info& o = rows[i];
+        o.bkind = d.bkind;
+        for (int k = 0; k < 3; ++k) {
+            o.slo[k] = d.slo[k];
+            o.shi[k] = d.shi[k];
+            o.wlo[k] = d.wlo[k];
+            o.whi[k] = d.whi[k];
+        }
+        for (int k = 0; k < 6; ++k) o.tight[k] = B.wtight[6 * i + (size_t)k];
+        o.tslack = d.tslack;
+        o.back = d.back;
+        o.wback = d.wback;
+    }
+    if (R) *R = B.R;
+    if (r_limit) *r_limit = B.r_limit;
+    if (bounded) *bounded = (!B.unbounded && B.geoms.size() <= (size_t)ptd::kLdsGeoms) ? 1 : 0;
+    if (abs_slack) *abs_slack = B.abs_slack;
+    if (wb_tslack) *wb_tslack = B.wb_tslack;
     return PT_OK;
 }

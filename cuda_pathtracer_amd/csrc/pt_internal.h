@@ -99,6 +99,9 @@ struct BoundsHost {
     std::vector<float> wtight;       // bkind 3: the widened cube's world hull before the pad, rounded outward,
                                      // (lo, hi) of axis r at [6 * geom + 2 * r] (update_bounds; find_room's room.in)
     double scene_ext = 0.0;          // max |coordinate| over every surface and the camera position
+    double R = 0.0;                  // update_bounds: the largest |coordinate| of a ray origin the bounds are sized for
+    double r_limit = 0.0;            // update_bounds: the largest R for which no bound form of this scene overflows
+    bool unbounded = false;          // R > r_limit: every geom carries a bound that claims nothing (update_bounds)
     float abs_slack = 0.0f;          // SceneDev::abs_slack
     float wb_tslack = 0.0f;          // SceneDev::wb_tslack
     ptd::RoomDev room{};             // SceneDev::room

@@ -3545,6 +3545,215 @@ __global__ void k_selftest_exact(uint64_t n, uint32_t seed, unsigned long long* 
     if (fast) atomicAdd(out + 2, fast);
 }
 
+// pt_selftest_bounds: every bound form of the bounded closest hit against exact_geom_literal, per (ray,
+// geom) pair of a prepared scene (include/pt_amd.h for the ray classes and the forms).  The forms are the
+// render kernels' own functions, called with the per-ray values intersect_bounded derives (rl, rlt, rinf,
+// invd, dd, rdd, rsdd), and a float form's value is tagged as intersect_bounded's `insert` tags it.
+struct SelfBox {
+    float lo[3], hi[3];   // the scene's box: every surface and the camera
+    float R;              // the largest |coordinate| of an origin inside the bounds' precondition
+};
+struct SelfCounts {
+    unsigned long long pairs[5], bad_tagged[5], bad_float[5], rays[6], skipped[6];
+};
+__global__ __launch_bounds__(kBlock) void k_selftest_bounds(const SceneDev S, const CamDev cam, const FlagsDev fl,
+                                                            const TileDev T, const SelfBox W, uint64_t n, uint32_t seed,
+                                                            pt_bounds_report* rep) {
+    __shared__ LGeom s_geoms[kLdsGeoms];
+    __shared__ SelfCounts s_cnt;
+    for (int k = threadIdx.x; k < (int)(sizeof(SelfCounts) / 8); k += blockDim.x)
+        reinterpret_cast<unsigned long long*>(&s_cnt)[k] = 0ull;
+    stage_geoms(S, s_geoms);
+    __syncthreads();
+    const auto* B = as_const(S.bgeoms);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t h = utilhash((uint32_t)i ^ seed ^ (uint32_t)(i >> 32) * 0x9e3779b9u);
+        auto next = [&]() { h = utilhash(h + 0x7f4a7c15u); return h; };
+        auto u01 = [&]() { return (float)(next() >> 8) * 0x1p-24f; };   // [0, 1)
+        auto usym = [&]() { return u01() * 2.0f - 1.0f; };              // [-1, 1)
+        auto unit = [&]() {                                             // uniform on the sphere
+            const float z = usym(), phi = u01() * kTWO_PI, r = sqrtf(fmaxf(0.0f, 1.0f - z * z));
+            return normalize(F3(r * cosf(phi), r * sinf(phi), z));
+        };
+        auto in_box = [&]() {
+            const float a = u01(), b = u01(), c = u01();
+            return F3(W.lo[0] + a * (W.hi[0] - W.lo[0]), W.lo[1] + b * (W.hi[1] - W.lo[1]),
+                      W.lo[2] + c * (W.hi[2] - W.lo[2]));
+        };
+        auto ulps = [&](float x) {   // x moved by 0, +-1 or +-4 floats (through zero where it is that near)
+            const int step[5] = {0, 1, -1, 4, -4};
+            int32_t b = (int32_t)__float_as_uint(x);
+            b = b < 0 ? (int32_t)(0x80000000u - (uint32_t)b) : b;   // ordered: -x <-> -bits(x)
+            b += step[next() % 5u];
+            return __uint_as_float(b < 0 ? 0x80000000u - (uint32_t)b : (uint32_t)b);
+        };
+        int cls = (int)(i % 6u);
+        f3 ro = in_box(), rd = unit();
+        const int gsel = (int)(next() % (uint32_t)S.ngeoms);   // the geom classes 1, 3 and 4 aim at
+        const LGeom& Lg = s_geoms[gsel];
+        if (cls == 1) {
+            // the exact hit of the base ray on geom gsel, or on the first geom after it that the ray hits
+            float t = -1.0f;
+            int code = -1, gh = gsel;
+            f3 obj = F3(0, 0, 0);
+            bool outside = true;
+            for (int k = 0; k < S.ngeoms && !(t > 0.0f); ++k) {
+                gh = gsel + k < S.ngeoms ? gsel + k : gsel + k - S.ngeoms;
+                t = exact_geom_literal(s_geoms[gh], ro, rd, code, obj, outside);
+            }
+            if (t > 0.0f) {
+                const LGeom& Lh = s_geoms[gh];
+                const f3 nrm = Lh.type == PT_GEOM_CUBE ? box_normal(Lh, code) : sphere_normal(Lh, obj, outside);
+                ro = point_on_ray(ro, rd, t) + 0.0001f * nrm;   // shade / shade_from
+                if (next() & 1u) {
+                    rd = normalize(nrm + 0.999f * unit());      // cosine-distributed about the normal
+                } else {
+                    const f3 tg = normalize(cross(nrm, unit()));
+                    rd = normalize(tg + (usym() * 1e-3f) * nrm);   // grazing, either side
+                }
+            } else {
+                cls = 0;
+            }
+        } else if (cls == 2) {
+            const uint32_t k = next() % 3u, mode = next() % 4u, sg = next();
+            const float z0 = __uint_as_float(sg & 0x80000000u), z1 = __uint_as_float((sg << 1) & 0x80000000u);
+            const float den = __uint_as_float((sg & 0x80000000u) | (next() & 0x007fffffu) | 1u);
+            float c[3] = {rd.x, rd.y, rd.z};
+#pragma unroll
+            for (uint32_t q = 0; q < 3; ++q) {
+                if (q == k) c[q] = mode == 3u ? den : (mode == 1u ? -0.0f : (mode == 0u ? 0.0f : z0));
+                if (q == (k + 1u) % 3u && mode == 2u) c[q] = z1;
+            }
+            rd = normalize(F3(c[0], c[1], c[2]));
+        } else if (cls == 3) {
+            const f3 qo = xform_point(Lg.inv, ro);
+            f3 tq;
+            if (Lg.type == PT_GEOM_CUBE) {
+                const uint32_t m = next();
+                tq = F3(m & 1u ? 0.5f : -0.5f, m & 2u ? 0.5f : -0.5f, m & 4u ? 0.5f : -0.5f);
+                if (m & 8u) {   // a point of an edge instead of the corner
+                    const float e = usym() * 0.5f;
+                    const uint32_t ax = (m >> 4) % 3u;
+                    tq = F3(ax == 0u ? e : tq.x, ax == 1u ? e : tq.y, ax == 2u ? e : tq.z);
+                }
+            } else {
+                // a silhouette point p of the sphere as the origin sees it: |p| = 0.5 and p . (p - qo) = 0
+                const float l2 = dot(qo, qo);
+                const f3 u = unit();
+                if (l2 > 0.26f) {
+                    const f3 ax = qo * (1.0f / sqrtf(l2));
+                    const f3 pe = normalize(cross(ax, u));
+                    const float along = 0.25f / sqrtf(l2);
+                    tq = along * ax + sqrtf(fmaxf(0.0f, 0.25f - along * along)) * pe;
+                } else {
+                    tq = 0.5f * u;
+                }
+            }
+            const f3 tw = xform_point(Lg.xf, tq);
+            rd = normalize(F3(ulps(tw.x), ulps(tw.y), ulps(tw.z)) - ro);
+        } else if (cls == 4) {
+            const float half = Lg.type == PT_GEOM_CUBE ? 0.499f : 0.28f;   // (0.28 sqrt(3) < 0.5)
+            const float a = usym(), b = usym(), c = usym();
+            ro = xform_point(Lg.xf, F3(a * half, b * half, c * half));
+        } else if (cls == 5) {
+            TileDev Tt = T;
+            Tt.iter_first = 1 + (int32_t)(next() & 0xffffu);
+            PathReg p;
+            raygen_at(cam, fl, Tt, 0, 0, (int)(next() % (uint32_t)T.npix), p);
+            ro = p.o;
+            rd = p.d;
+        }
+        // the per-ray values of intersect_bounded, and its precondition
+        const float rl = __builtin_amdgcn_sqrtf(dot(rd, rd));
+        const bool inside = fabsf(ro.x) <= W.R && fabsf(ro.y) <= W.R && fabsf(ro.z) <= W.R;   // (false for a NaN)
+        if (!(rl > 0.5f && rl < 2.0f) || rd.x != rd.x || rd.y != rd.y || rd.z != rd.z || !inside) {
+            atomicAdd(&s_cnt.skipped[cls], 1ull);
+            continue;
+        }
+        atomicAdd(&s_cnt.rays[cls], 1ull);
+        const float rinf = fmaxf(fmaxf(fabsf(ro.x), fabsf(ro.y)), fabsf(ro.z));
+        const f3 invd = F3(__builtin_amdgcn_rcpf(rd.x), __builtin_amdgcn_rcpf(rd.y), __builtin_amdgcn_rcpf(rd.z));
+        const float rlt = rl * S.wb_tslack;
+        const float dd = dot(rd, rd), rdd = __builtin_amdgcn_rcpf(dd), rsdd = __builtin_amdgcn_rsqf(dd);
+        auto judge = [&](int slot, bool flt, uint32_t form, uint32_t tag, int gi, float t) {
+            if (tag < 0x7f800000u && __uint_as_float(tag) - S.abs_slack <= t) return;
+            atomicAdd(flt ? &s_cnt.bad_float[slot] : &s_cnt.bad_tagged[slot], 1ull);
+            if (atomicCAS(&rep->has_first, 0u, 1u) == 0u) {
+                rep->first_geom = (uint32_t)gi;
+                rep->first_form = form;
+                rep->first_origin[0] = __float_as_uint(ro.x);
+                rep->first_origin[1] = __float_as_uint(ro.y);
+                rep->first_origin[2] = __float_as_uint(ro.z);
+                rep->first_dir[0] = __float_as_uint(rd.x);
+                rep->first_dir[1] = __float_as_uint(rd.y);
+                rep->first_dir[2] = __float_as_uint(rd.z);
+                rep->first_bound = tag;
+                rep->first_t = __float_as_uint(t);
+            }
+        };
+        auto ftag = [&](float lo, int gi) { return lo == kInf ? 0x7f800000u : tag_bound(lo, (uint32_t)gi); };   // `insert`
+        auto exact = [&](int gi) {
+            int code;
+            f3 obj = F3(0, 0, 0);
+            bool outside;
+            return exact_geom_literal(s_geoms[gi], ro, rd, code, obj, outside);
+        };
+        uint32_t rt[6] = {0x7f800000u, 0x7f800000u, 0x7f800000u, 0x7f800000u, 0x7f800000u, 0x7f800000u};
+        if (S.room.n > 0) {
+            int k = 0;
+            bound_room_tagged(S, ro, invd, rlt, [&](uint32_t t) { rt[k++] = t; });
+        }
+        for (int j = S.bk[3]; j < S.bk[4]; ++j) {
+            const int gi = B[j].orig;
+            const float t = exact(gi);
+            if (!(t > 0.0f)) continue;
+            atomicAdd(&s_cnt.pairs[2], 1ull);
+            judge(2, false, 0u, bound_wbox_tagged(B[j], ro, invd, rlt, (uint32_t)gi), gi, t);
+            judge(2, true, 1u, ftag(bound_geom<3, false>(B[j], ro, rd, invd, rl, rinf), gi), gi, t);
+            judge(2, true, 2u, ftag(bound_geom<3, true>(B[j], ro, rd, invd, rl, rinf), gi), gi, t);
+            if (j < S.bk[3] + S.room.n) {   // a wall of the room: its slot of the group's six
+                uint32_t tag = 0x7f800000u;
+#pragma unroll
+                for (int q = 0; q < 6; ++q)
+                    if (rt[q] < 0x7f800000u && (int)(rt[q] & 31u) == gi) tag = rt[q];
+                atomicAdd(&s_cnt.pairs[4], 1ull);
+                judge(4, false, 3u, tag, gi, t);
+            }
+        }
+        for (int j = S.bk[4]; j < S.bk[5]; ++j) {
+            const int gi = B[j].orig;
+            const float t = exact(gi);
+            if (!(t > 0.0f)) continue;
+            atomicAdd(&s_cnt.pairs[3], 1ull);
+            judge(3, false, 0u, bound_sphere_tagged(B[j], ro, rd, dd, rl, rinf, rdd, rsdd, (uint32_t)gi), gi, t);
+            judge(3, true, 1u, ftag(bound_geom<4, false>(B[j], ro, rd, invd, rl, rinf), gi), gi, t);
+            judge(3, true, 2u, ftag(bound_geom<4, true>(B[j], ro, rd, invd, rl, rinf), gi), gi, t);
+        }
+        for (int j = S.bk[1]; j < S.bk[2]; ++j) {
+            const int gi = B[j].orig;
+            const float t = exact(gi);
+            if (!(t > 0.0f)) continue;
+            atomicAdd(&s_cnt.pairs[0], 1ull);
+            judge(0, false, 0u, bound_obox_tagged(B[j], ro, rd, rl, rsdd, (uint32_t)gi), gi, t);
+            judge(0, true, 1u, ftag(bound_geom<1, false>(B[j], ro, rd, invd, rl, rinf), gi), gi, t);
+            judge(0, true, 2u, ftag(bound_geom<1, true>(B[j], ro, rd, invd, rl, rinf), gi), gi, t);
+        }
+        for (int j = S.bk[2]; j < S.bk[3]; ++j) {   // (spheres of bkind 2 have no tagged form)
+            const int gi = B[j].orig;
+            const float t = exact(gi);
+            if (!(t > 0.0f)) continue;
+            atomicAdd(&s_cnt.pairs[1], 1ull);
+            judge(1, true, 1u, ftag(bound_geom<2, false>(B[j], ro, rd, invd, rl, rinf), gi), gi, t);
+            judge(1, true, 2u, ftag(bound_geom<2, true>(B[j], ro, rd, invd, rl, rinf), gi), gi, t);
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < (int)(sizeof(SelfCounts) / 8); k += blockDim.x) {
+        const unsigned long long v = reinterpret_cast<unsigned long long*>(&s_cnt)[k];
+        if (v) atomicAdd(reinterpret_cast<unsigned long long*>(rep) + k, v);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Host context
 // ------------------------------------------------------------------------------------------
@@ -4827,6 +5036,89 @@ int pt_selftest_exact(uint64_t n, uint32_t seed, uint64_t* mismatches, uint64_t*
     *mismatches = h[0];
     *tripped = h[1];
     *fast = h[2];
+    return PT_OK;
+}
+
+int pt_selftest_bounds(const pt_scene* scene, const pt_flags* flags, uint64_t n, uint32_t seed, pt_bounds_report* report) {
+    static_assert(offsetof(pt_bounds_report, has_first) == sizeof(SelfCounts) && sizeof(pt_bounds_report) == 264,
+                  "k_selftest_bounds adds its counters over the report's first words");
+    if (!scene || !report) return pt::fail(PT_ERR_ARG, "null argument");
+    const auto& S = *reinterpret_cast<const pt::Scene*>(scene);
+    if (!S.finalized) return pt::fail(PT_ERR_ARG, "scene not finalized (pt_scene_finalize)");
+    if (S.geoms.empty()) return pt::fail(PT_ERR_ARG, "scene has no geometry");
+    if (S.geoms.size() > (size_t)kLdsGeoms || !S.triangles.empty())
+        return pt::fail(PT_ERR_ARG, "the scene does not take the bounded closest hit (more than 32 geoms, or meshes)");
+    pt_flags f;
+    if (flags) f = *flags;
+    else pt_flags_default(&f);
+    // the scene as pt_create prepares it
+    pt::BoundsHost bh = pt::make_dgeoms(S);
+    pt::update_bounds(bh, f.aperture);   // (ends with find_room)
+    if (bh.unbounded) return pt::fail(PT_ERR_ARG, "the scene is beyond the bounds' range (pt_scene_bound_info): no bound to check");
+    std::vector<DGeom> ordered;
+    SceneDev sd;
+    std::memset(&sd, 0, sizeof sd);
+    pt::bound_order(bh, ordered, sd.bk);
+    if (ordered.size() != bh.geoms.size()) return pt::fail(PT_ERR_ARG, "geom with an unknown bound kind");
+    sd.ngeoms = (int32_t)bh.geoms.size();
+    sd.abs_slack = bh.abs_slack;
+    sd.wb_tslack = bh.wb_tslack;
+    sd.room = bh.room;
+    CamDev cam;
+    std::memset(&cam, 0, sizeof cam);
+    for (int k = 0; k < 3; ++k) {
+        cam.pos[k] = S.camera.position[k];
+        cam.view[k] = S.camera.view[k];
+        cam.up[k] = S.camera.up[k];
+        cam.right[k] = S.camera.right[k];
+    }
+    cam.pl[0] = S.camera.pixel_length[0];
+    cam.pl[1] = S.camera.pixel_length[1];
+    cam.res[0] = S.camera.res[0];
+    cam.res[1] = S.camera.res[1];
+    const long long npix = (long long)cam.res[0] * cam.res[1];
+    if (cam.res[0] <= 0 || cam.res[1] <= 0 || npix > 0x7fffffffLL) return pt::fail(PT_ERR_ARG, "bad camera resolution");
+    FlagsDev fd;
+    std::memset(&fd, 0, sizeof fd);
+    fd.ssaa = f.ssaa;
+    fd.dof = f.dof;
+    fd.aperture = f.aperture;
+    fd.focal = f.focal_dist;
+    const TileDev tile{cam.res[0], 0, 1, (int32_t)npix, 1, (int32_t)npix, S.depth, 1, 0};
+    SelfBox box;   // every surface and the camera, as make_dgeoms takes the scene's extent
+    for (int k = 0; k < 3; ++k) box.lo[k] = box.hi[k] = cam.pos[k];
+    for (const DGeom& d : bh.geoms)
+        for (int corner = 0; corner < 8; ++corner)
+            for (int r = 0; r < 3; ++r) {
+                double v = d.xf.c[3][r];
+                for (int k = 0; k < 3; ++k) v += (double)d.xf.c[k][r] * ((corner >> k) & 1 ? 0.5 : -0.5);
+                box.lo[r] = std::min(box.lo[r], (float)v);
+                box.hi[r] = std::max(box.hi[r], (float)v);
+            }
+    box.R = (float)bh.R;
+    if ((double)box.R > bh.R) box.R = std::nextafter(box.R, 0.0f);
+
+    DGeom *d_geoms = nullptr, *d_bgeoms = nullptr;
+    pt_bounds_report* d_rep = nullptr;
+    const size_t gbytes = bh.geoms.size() * sizeof(DGeom);
+    hipError_t e = hipMalloc(&d_geoms, gbytes);
+    if (e == hipSuccess) e = hipMalloc(&d_bgeoms, gbytes);
+    if (e == hipSuccess) e = hipMalloc(&d_rep, sizeof *d_rep);
+    if (e == hipSuccess) e = hipMemcpy(d_geoms, bh.geoms.data(), gbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_bgeoms, ordered.data(), gbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_rep, 0, sizeof *d_rep);
+    if (e == hipSuccess) {
+        sd.geoms = d_geoms;
+        sd.bgeoms = d_bgeoms;
+        const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, 1024));
+        hipLaunchKernelGGL(k_selftest_bounds, dim3(grid), dim3(kBlock), 0, nullptr, sd, cam, fd, tile, box, n, seed, d_rep);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(report, d_rep, sizeof *report, hipMemcpyDeviceToHost);   // (synchronises)
+    (void)hipFree(d_geoms);
+    (void)hipFree(d_bgeoms);
+    (void)hipFree(d_rep);
+    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("selftest: ") + hipGetErrorString(e));
     return PT_OK;
 }
 

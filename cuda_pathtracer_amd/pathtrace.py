@@ -245,6 +245,44 @@ class Scene:
         return {"walls": int(n.value), "faces": [int(v) for v in faces], "lo": [float(v) for v in lo],
                 "hi": [float(v) for v in hi]}
 
+    def bound_info(self, gui: GuiDataContainer | None = None) -> dict:
+        """The widened bounds a PathTracer of this scene with these flags would use (pt_scene_bound_info:
+        the host's scene preparation alone, no device): R, r_limit, bounded, abs_slack, wb_tslack and one
+        dict per geom (bkind, slo, shi, wlo, whi, tight, tslack, back, wback)."""
+        if not hasattr(lib(), "pt_scene_bound_info"):
+            raise N.NativeLibraryError("the loaded library (PT_AMD_LIB) predates pt_scene_bound_info")
+        flags = (gui or GuiDataContainer()).to_c()
+        ng = self.counts()[0]
+        rows = (N.BoundInfo * max(ng, 1))()
+        R, lim, bounded = C.c_double(), C.c_double(), C.c_int32()
+        slack, wbts = C.c_float(), C.c_float()
+        check_pt(lib().pt_scene_bound_info(self._h, C.byref(flags), rows, ng, C.byref(R), C.byref(lim),
+                                           C.byref(bounded), C.byref(slack), C.byref(wbts)))
+        geoms = [{"bkind": int(r.bkind), "slo": list(r.slo), "shi": list(r.shi), "wlo": list(r.wlo),
+                  "whi": list(r.whi), "tight": list(r.tight), "tslack": float(r.tslack), "back": float(r.back),
+                  "wback": float(r.wback)} for r in list(rows)[:ng]]
+        return {"R": float(R.value), "r_limit": float(lim.value), "bounded": bool(bounded.value),
+                "abs_slack": float(slack.value), "wb_tslack": float(wbts.value), "geoms": geoms}
+
+    def selftest_bounds(self, gui: GuiDataContainer | None = None, n: int = 1 << 16, seed: int = 1) -> dict:
+        """The device's per-pair check of every bound form of this scene against the exact test
+        (pt_selftest_bounds): pair and violation counts per kind (bkind 1, 2, 3, 4, room), rays per class,
+        and the first violating record, if any."""
+        if not hasattr(lib(), "pt_selftest_bounds"):
+            raise N.NativeLibraryError("the loaded library (PT_AMD_LIB) predates pt_selftest_bounds")
+        flags = (gui or GuiDataContainer()).to_c()
+        r = N.BoundsReport()
+        check_pt(lib().pt_selftest_bounds(self._h, C.byref(flags), int(n), int(seed), C.byref(r)))
+        kinds = ("1", "2", "3", "4", "room")
+        first = None
+        if r.has_first:
+            first = {"geom": int(r.first_geom), "form": int(r.first_form),
+                     "origin_bits": [hex(v) for v in r.first_origin], "dir_bits": [hex(v) for v in r.first_dir],
+                     "bound_bits": hex(r.first_bound), "t_bits": hex(r.first_t)}
+        return {"pairs": dict(zip(kinds, map(int, r.pairs))), "bad_tagged": dict(zip(kinds, map(int, r.bad_tagged))),
+                "bad_float": dict(zip(kinds, map(int, r.bad_float))), "rays": [int(v) for v in r.rays],
+                "skipped": [int(v) for v in r.skipped], "first": first}
+
     def materials(self):
         nm = self.counts()[1]
         arr = (N.Material * max(nm, 1))()

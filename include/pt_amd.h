@@ -233,6 +233,25 @@ int pt_scene_bvh_tcull(const pt_scene* s, uint32_t* words, int32_t cap, double* 
  * defaults) would bound as one group, derived without a device; outputs as pt_ctx_room_info's. */
 int pt_scene_room_info(const pt_scene* s, const pt_flags* flags, int32_t* walls, int32_t* faces, float* lo,
                        float* hi);
+/* Inspection (host only): the widened bounds of the bounded closest hit that a context
+ * created from this scene with these flags (NULL: the defaults) would use, derived without a device.
+ * Per geom, min(geom count, cap) rows: the bound kind (0 none, 1 oriented cube, 2 sphere, 3 world-box
+ * cube, 4 uniformly scaled sphere), the widened object-space slabs, the widened world box and the tight
+ * planes of a world-box cube ((lo, hi) of axis a at tight[2a]; zeros for other kinds; a uniformly
+ * scaled sphere keeps its centre in wlo and its squared inverse scale and that value's reciprocal in
+ * whi[0], whi[1]), the relative slack and the pull-back constants.  *R: the largest |coordinate| of a ray origin the bounds are sized
+ * for; *r_limit: the largest R for which this scene's bound forms cannot overflow; *bounded: 1 when the
+ * context runs the bounds pass, 0 when R exceeds r_limit and every geom is exact-tested for every ray
+ * (the rows then hold bounds that claim nothing); *abs_slack, *wb_tslack as the kernels read them.  Any
+ * pointer may be null. */
+typedef struct pt_bound_info {
+    int32_t bkind;
+    float slo[3], shi[3], wlo[3], whi[3];
+    float tight[6];
+    float tslack, back, wback;
+} pt_bound_info;   /* 88 bytes */
+int pt_scene_bound_info(const pt_scene* s, const pt_flags* flags, pt_bound_info* rows, int32_t cap, double* R,
+                        double* r_limit, int32_t* bounded, float* abs_slack, float* wb_tslack);
 
 /* ---- render context -------------------------------------------------------------------- */
 /* pathtraceInit: uploads the scene to the current HIP device, allocates SoA path buffers for
@@ -374,6 +393,37 @@ int pt_selftest_math(uint64_t n, uint32_t seed, uint64_t* mismatches);
  * NaN) or, for a hit, whose slab code, object-space point or side differ; *tripped = pairs whose gate
  * tripped; *fast = pairs the fast path answered.  Synchronous. */
 int pt_selftest_exact(uint64_t n, uint32_t seed, uint64_t* mismatches, uint64_t* tripped, uint64_t* fast);
+/* Device self-check of the bounded closest hit's lower bounds, per (ray, geom) pair.
+ * The scene is prepared as pt_create prepares it (geom table, widened bounds with the flags' aperture,
+ * room, bound order) and uploaded; n rays are generated on the device from `seed`, and every ray is
+ * checked against every bounded geom with the functions the render kernels call: where the literal
+ * exact test returns t > 0, every bound form the kernels can apply to that geom must be a candidate
+ * (tag below +inf's bits) whose bound, less the scene's absolute slack, does not exceed t.  Forms: 0 the
+ * tagged form of the geom's kind (world-box cube, oriented cube, uniform sphere), 1 and 2 the float form
+ * with early returns and with selects (tagged as the pass tags it), 3 a room wall's slot in the grouped
+ * room bound.  Rays take their class from their index (i mod 6) and stay inside the bounds' precondition
+ * (every origin coordinate within R, direction length in (0.5, 2), no NaN; others are counted in
+ * `skipped`, by class): 0 origin uniform in the scene's box, uniform direction; 1 rays departing from the exact hit
+ * of such a ray on a geom, pulled back and lifted as the shader does, half cosine-distributed about the
+ * normal and half grazing (|cos| < 1e-3); 2 directions with one or two components exactly +-0 or with a
+ * denormal component; 3 rays aimed at a cube's corner or edge or at a sphere's silhouette point, the
+ * world-space target moved by 0, +-1 or +-4 ulp per coordinate; 4 origins inside a geom; 5 rays of the
+ * scene's camera (lens samples when the flags' DoF is on).  A class-1 ray whose base ray hits nothing
+ * counts in class 0.  Scenes the context does not bound (more than 32 geoms, meshes, or beyond the
+ * bounds' range: pt_scene_bound_info) are an argument error.  Synchronous. */
+typedef struct pt_bounds_report {
+    uint64_t pairs[5];        /* pairs with t > 0 per kind: bkind 1, 2, 3, 4, walls of the room */
+    uint64_t bad_tagged[5];   /* violations of the tagged form (the room: of the wall's slot) */
+    uint64_t bad_float[5];    /* violations of the float forms */
+    uint64_t rays[6];         /* rays checked per class */
+    uint64_t skipped[6];      /* rays per class that left the precondition, not checked */
+    uint32_t has_first;       /* a violation was recorded below (any one of them) */
+    uint32_t first_geom, first_form;
+    uint32_t first_origin[3], first_dir[3];   /* float bits */
+    uint32_t first_bound, first_t;            /* the tag, and t's bits */
+    uint32_t pad_;
+} pt_bounds_report;   /* 264 bytes */
+int pt_selftest_bounds(const pt_scene* s, const pt_flags* flags, uint64_t n, uint32_t seed, pt_bounds_report* report);
 
 /* ---- texture input --------------------------------------------------------------------- */
 /* Texture::load (sceneStructs.h:171-175) = stbi_load(file, &w, &h, &comp, 0) for JPEG data:

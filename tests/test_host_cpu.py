@@ -49,6 +49,10 @@ def test_abi_struct_sizes_match_header():
     assert C.sizeof(N.Material) == 48 and C.sizeof(N.Geom) == 272
     assert C.sizeof(N.Triangle) == 124 and C.sizeof(N.BvhNode) == 40
     assert C.sizeof(N.Camera) == 4 * (2 + 3 * 5 + 4)
+    # the rows of pt_scene_bound_info and the report of pt_selftest_bounds, sized in the header's comments
+    for struct, size, cls in (("pt_bound_info", 88, N.BoundInfo), ("pt_bounds_report", 264, N.BoundsReport)):
+        assert re.search(r"\}\s*%s;\s*/\*\s*%d bytes" % (struct, size), text)
+        assert C.sizeof(cls) == size
 
 
 def _f(a):
