@@ -230,6 +230,18 @@ class DisplayParams(C.Structure):
         return p
 
 
+class EnvParams(C.Structure):
+    """pt_env_params; EnvParams.default() = pt_env_params_default (scale 1, no rotation, size 0: derived)."""
+    _fields_ = [("scale", C.c_float), ("rotate_deg", C.c_float * 3), ("size", C.c_int32)]
+
+    @classmethod
+    def default(cls) -> "EnvParams":
+        p = cls()
+        lib().pt_env_params_default(C.byref(p))
+        return p
+
+
+assert C.sizeof(EnvParams) == 20
 DISPLAY_MANUAL, DISPLAY_AUTO = 0, 1                                      # PT_DISPLAY_* exposure modes
 DISPLAY_NONE, DISPLAY_REINHARD, DISPLAY_ACES, DISPLAY_HABLE = 0, 1, 2, 3  # curves
 DISPLAY_LINEAR, DISPLAY_SRGB = 0, 1                                      # transfers
@@ -441,6 +453,15 @@ SIGNATURES = {
     "pt_display_info": (_I, [_P, _P, _IP, _FP, _IP]),
     "pt_display_tables": (None, [_P, _P, _FP]),
     "pt_preview_display": (_I, [_P, _I, _P, _P, _I, _P]),
+    "pt_env_params_default": (None, [C.POINTER(EnvParams)]),
+    "pt_scene_set_environment": (_I, [_P, _I, _I, _P, C.POINTER(EnvParams)]),
+    "pt_scene_set_environment_octa": (_I, [_P, _I, _P, C.POINTER(EnvParams)]),
+    "pt_scene_load_environment": (_I, [_P, C.c_char_p, C.POINTER(EnvParams)]),
+    "pt_scene_clear_environment": (_I, [_P]),
+    "pt_scene_get_environment": (_I, [_P, _IP, C.POINTER(EnvParams), _P, C.c_int64]),
+    "pt_decode_hdr": (_I, [C.c_char_p, C.c_int64, _IP, _IP, _P, C.c_int64]),
+    "pt_env_eval": (_I, [_P, C.c_int64, _P, _P, _P]),
+    "pt_env_eval_host": (_I, [_P, C.c_int64, _P, _P]),
 }
 
 _lib = None
@@ -466,8 +487,11 @@ def _preload_torch() -> None:
 # pt_jpeg_*, pt_preview_jpeg: the A/B against the build before the JPEG encoder; pt_png_*, pt_preview_png: the
 # A/B against the build before the PNG encoder; pt_hdr_*, pt_preview_hdr: the A/B against the build before the
 # HDR encoder; pt_exr_*, pt_preview_exr: the A/B against the build before the OpenEXR encoder; pt_display_*, pt_preview_display: scripts/display_time.py's A/B against the build before the display
-# transform).
-_OPTIONAL = {"pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
+# transform; pt_env_*, pt_scene_*_environment*, pt_decode_hdr: the A/B against the build before the environment).
+_OPTIONAL = {"pt_env_params_default", "pt_scene_set_environment", "pt_scene_set_environment_octa",
+             "pt_scene_load_environment", "pt_scene_clear_environment", "pt_scene_get_environment", "pt_decode_hdr",
+             "pt_env_eval", "pt_env_eval_host",
+             "pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
              "pt_ctx_exact_counts", "pt_selftest_exact", "pt_scene_bound_info", "pt_selftest_bounds",
              "pt_moments_create",
              "pt_moments_destroy", "pt_moments_reset", "pt_moments_update", "pt_moments_info", "pt_moments_variance",

@@ -19,7 +19,16 @@ struct TextureHost {
     std::vector<uint8_t> pixels;
 };
 
+// The environment (pt_env.cpp): the padded octahedral map as the device reads it.
+struct EnvHost {
+    int32_t n = 0;               // 0: none
+    pt_env_params params{};      // as given (size: the n in use)
+    float rot[9] = {};           // row-major world-to-map rotation of params.rotate_deg
+    std::vector<float> rgba;     // (n + 2)^2 * 4
+};
+
 struct Scene {
+    EnvHost env;
     std::vector<pt_geom> geoms;
     std::vector<pt_material> materials;
     std::vector<pt_triangle> tris_load;     // mesh triangles in load order (ids = index here)
@@ -54,6 +63,8 @@ int build_bvh_device(Scene& S, double* ms);
 int decode_jpeg(const uint8_t* data, size_t size, int32_t* width, int32_t* height, int32_t* components,
                 std::vector<uint8_t>* pixels);
 int load_texture_file(TextureHost& t);
+// Environment (pt_env.cpp): a Radiance .hdr file resampled onto the scene's octahedral map
+int load_environment_file(Scene& S, const std::string& path, const pt_env_params* params);
 // Denoiser (pt_denoise.hip): the argument checks of pt_denoiser_run that need no device
 int denoise_check(const pt_denoise_params* p, float samples);
 int denoise_var_check(const pt_denoise_var_params* p, float samples);

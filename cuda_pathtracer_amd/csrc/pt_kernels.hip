@@ -35,6 +35,7 @@
 
 #include "lookback.h"
 #include "pt_device.h"
+#include "pt_env_dev.h"
 #include "pt_internal.h"
 #include "pt_ctx.h"
 #include "../../include/sc_amd.h"
@@ -135,7 +136,10 @@ struct KArgs {
     int32_t tchunk;        // k_traverse: largest ray chunk per ticket grab (kTravChunk; PT_AMD_TCHUNK)
     int32_t stack_rows;    // k_traverse: LDS stack entries per thread (HybStack)
     const uint32_t* cmask; // first bounce: per 64 tile pixels, the geoms its camera rays can hit (null: all)
+    EnvDev env;            // the environment a miss is shaded with (the ENV instantiations only; map null: none)
 };
+static_assert(offsetof(KArgs, env) == offsetof(KArgs, cmask) + 8 && sizeof(KArgs) - offsetof(KArgs, env) - sizeof(EnvDev) < 16,
+              "the environment is appended to the kernel arguments (SortArgs follows KArgs: fresh_param)");
 
 // ------------------------------------------------------------------------------------------
 // Intersection (computeIntersections, pathtrace.cu:229-298)
@@ -1327,9 +1331,14 @@ __device__ __forceinline__ int slot_pixel(const CamDev& cam, const TileDev& T, i
 // shade()'s two exits that draw no random numbers (pathtrace.cu:318-330): a miss (colour 0) and an
 // emissive hit (colour x material colour x emittance).  True if the path ends there; p.c is then
 // its final colour.  The sorted pipeline takes these exits one launch early (k_sort_produce).
-template <class MT>
+// ENV (a context with an environment): a miss keeps its throughput in p.c and the caller
+// multiplies it by the environment's radiance along p.d (env_lookup) once the path is dead.
+template <bool ENV = false, class MT>
 __device__ __forceinline__ bool shade_ends(const Hit& h, const MT* mats, PathReg& p) {
-    if (h.t <= 0.0f) { p.c = F3(0, 0, 0); return true; }
+    if (h.t <= 0.0f) {
+        if constexpr (!ENV) p.c = F3(0, 0, 0);
+        return true;
+    }
     const MT& m = mats[h.mat];
     if (m.emittance > 0.0f) {
         p.c = hadamard(p.c, F3(m.color[0], m.color[1], m.color[2]) * m.emittance);
@@ -1395,10 +1404,10 @@ __device__ __forceinline__ bool shade_from(const SceneDev& S, const FlagsDev& fl
 
 // Returns true if the path survives.  `idx` is the path's position in the (compacted, possibly
 // material-sorted) array — the RNG key of the reference (pathtrace.cu:315).
-template <class MT>
+template <bool ENV = false, class MT>
 __device__ __forceinline__ bool shade(const SceneDev& S, const FlagsDev& fl, int depth, int iter, int idx,
                                       PathReg& p, const Hit& h, const MT* mats, const float* frames = nullptr) {
-    if (shade_ends(h, mats, p)) return false;
+    if (shade_ends<ENV>(h, mats, p)) return false;
     return shade_from(S, fl, depth, iter, idx, p, h, point_on_ray(p.o, p.d, h.t), mats, frames);
 }
 
@@ -2463,10 +2472,18 @@ constexpr int kLaterWaves = 8; // (minimum waves per SIMD of the later-bounce ke
 // (profiles/r05_later_waves8_ab.txt).
 constexpr int kFirstWaves = 8;   // (minimum waves per SIMD of the analytic first-bounce kernels: 8 caps them at 64
                                  // VGPRs, one spilled; Cornell +1.8%, first bounce -11% per launch, profiles/r06_first_waves_ab.txt)
-template <bool FIRST, bool SPP1, int MESH>
+// MODE: the mesh mode (0 .. kAnalyticGM), plus kEnvBit when the context has an environment: a
+// compile-time choice, so the instantiations without one keep their code and their names; with it a miss ends the
+// path with its throughput x env_lookup(direction) instead of 0.
+constexpr int kEnvBit = 8;
+constexpr int bounce_mesh(int mode) { return mode & (kEnvBit - 1); }
+template <bool FIRST, bool SPP1, int MODE>
 // (kAnalyticGM took 8 waves unasked until the exact test's fast path kept its three slab axes live at once)
-__global__ __launch_bounds__(kBlock, (MESH == kMeshInline || MESH == kMeshPre) ? 1 : (FIRST ? kFirstWaves : kLaterWaves))
+__global__ __launch_bounds__(kBlock, (bounce_mesh(MODE) == kMeshInline || bounce_mesh(MODE) == kMeshPre) ? 1 : (FIRST ? kFirstWaves : kLaterWaves))
 void k_bounce(const KArgs A) {
+    constexpr int MESH = bounce_mesh(MODE);
+    constexpr bool ENV = (MODE & kEnvBit) != 0;
+    static_assert(!(ENV && MESH == kAnalyticSkip), "a context with an environment builds no camera masks");
     // scene tables sized to the scene (dynamic LDS, bounce_lds_bytes): geom rows, then materials
     extern __shared__ __align__(16) uint8_t s_dyn[];
     LGeom* s_geoms = reinterpret_cast<LGeom*>(s_dyn);
@@ -2700,8 +2717,11 @@ void k_bounce(const KArgs A) {
                 }
             }
 #endif
-            alive = lds_mats ? shade(A.S, A.fl, A.tile.depth, iter, key, p, h, s_mats, frames)
-                             : shade(A.S, A.fl, A.tile.depth, iter, key, p, h, A.S.mats, frames);
+            alive = lds_mats ? shade<ENV>(A.S, A.fl, A.tile.depth, iter, key, p, h, s_mats, frames)
+                             : shade<ENV>(A.S, A.fl, A.tile.depth, iter, key, p, h, A.S.mats, frames);
+            if constexpr (ENV) {   // the path is dead here: only its colour, direction and slot are live
+                if (!alive && h.t <= 0.0f) p.c = hadamard(p.c, env_lookup(A.env, p.d));
+            }
             if (!alive) {
                 emitted = p.c.x != 0.0f || p.c.y != 0.0f || p.c.z != 0.0f;
                 retire<SPP1>(A, p, my_it);
@@ -3952,6 +3972,7 @@ int build_cmask(pt_ctx* c) {
     const int ng = A.S.ngeoms;
     const char* off = std::getenv("PT_AMD_NO_CMASK");
     if ((off && std::strcmp(off, "1") == 0) || ng <= 0 || ng > kLdsGeoms || A.S.ntris > 0) return PT_OK;
+    if (A.env.map) return PT_OK;   // a pixel whose camera rays reach no geom is the sky: it is traced and shaded
     const size_t nblk = ((size_t)A.tile.npix + 63) / 64;
     if (!c->d_cmask)
         if (int rc = c->alloc(&c->d_cmask, nblk)) return rc;
@@ -4036,7 +4057,22 @@ int mesh_mode(const pt_ctx* c) {
 }
 
 using KernelFn = void (*)(const KArgs);
-KernelFn bounce_kernel(bool first, bool spp1, int mesh, bool skip = false, bool gmats = false) {   // mesh: 0, kMeshInline, kMeshPre
+KernelFn bounce_kernel_env(bool first, bool spp1, int mesh, bool gmats) {   // (no camera masks: no kAnalyticSkip)
+    if (mesh == 0 && gmats) {
+        constexpr int kGM = kAnalyticGM | kEnvBit;
+        static const KernelFn gm[4] = {k_bounce<false, false, kGM>, k_bounce<false, true, kGM>,
+                                       k_bounce<true, false, kGM>, k_bounce<true, true, kGM>};
+        return gm[(first ? 2 : 0) + (spp1 ? 1 : 0)];
+    }
+    static const KernelFn table[12] = {
+        k_bounce<false, false, 0 | kEnvBit>, k_bounce<false, false, 1 | kEnvBit>, k_bounce<false, false, 2 | kEnvBit>,
+        k_bounce<false, true, 0 | kEnvBit>,  k_bounce<false, true, 1 | kEnvBit>,  k_bounce<false, true, 2 | kEnvBit>,
+        k_bounce<true, false, 0 | kEnvBit>,  k_bounce<true, false, 1 | kEnvBit>,  k_bounce<true, false, 2 | kEnvBit>,
+        k_bounce<true, true, 0 | kEnvBit>,   k_bounce<true, true, 1 | kEnvBit>,   k_bounce<true, true, 2 | kEnvBit>};
+    return table[(first ? 6 : 0) + (spp1 ? 3 : 0) + mesh];
+}
+KernelFn bounce_kernel(bool first, bool spp1, int mesh, bool skip = false, bool gmats = false, bool env = false) {   // mesh: 0, kMeshInline, kMeshPre
+    if (env) return bounce_kernel_env(first, spp1, mesh, gmats);
     if (mesh == 0 && gmats) {   // (more materials than kLdsMats)
         static const KernelFn gm[4] = {k_bounce<false, false, kAnalyticGM>, k_bounce<false, true, kAnalyticGM>,
                                        k_bounce<true, false, kAnalyticGM>, k_bounce<true, true, kAnalyticGM>};
@@ -4111,7 +4147,8 @@ int launch_bounce(pt_ctx* c, bool first, bool spp1, int mesh, hipStream_t st, co
         if (int rc = prof_end(ev, st)) return rc;
     }
     if (int rc = prof_begin(c, st, first ? PT_KIND_FIRST_BOUNCE : PT_KIND_BOUNCE, &ev)) return rc;
-    hipLaunchKernelGGL(bounce_kernel(first, spp1, mesh, first && c->cmask_skip, a.S.nmats > kLdsMats || a.S.ngeoms > kLdsGeoms),
+    hipLaunchKernelGGL(bounce_kernel(first, spp1, mesh, first && c->cmask_skip, a.S.nmats > kLdsMats || a.S.ngeoms > kLdsGeoms,
+                                     a.env.map != nullptr),
                        dim3(c->grid_bounce[first]), dim3(kBlock),
                        bounce_lds_bytes(a.S, mesh), st, a);
     HIP_TRY(hipGetLastError());
@@ -4181,6 +4218,15 @@ int pt_create(const pt_scene* scene, const pt_flags* flags, const pt_shard* shar
     if (P > 0x7fffffffLL - 4096) return pt::fail(PT_ERR_ARG, "too many paths per pass");
     for (const auto& t : S.textures)
         if (t.pixels.empty()) return pt::fail(PT_ERR_ARG, "texture without pixels: " + t.path);
+    // An environment is shaded by the fused bounce kernels alone: the other pipelines refuse it.
+    if (S.env.n > 0) {
+        const pt_flags* f = flags;
+        if (f && f->sort_by_material)
+            return pt::fail(PT_ERR_ARG, "a scene with an environment cannot use material-sorted shading (sort_by_material)");
+        const char* pl = std::getenv("PT_PIPELINE");
+        if (pl && std::string(pl) == "split")
+            return pt::fail(PT_ERR_ARG, "a scene with an environment cannot use the split pipeline (PT_PIPELINE=split)");
+    }
 
     auto* c = new pt_ctx();
     auto bail = [&](int rc) { delete c; return rc; };
@@ -4323,6 +4369,18 @@ int pt_create(const pt_scene* scene, const pt_flags* flags, const pt_shard* shar
             return bail(pt::fail(PT_ERR_HIP, std::string("texture table upload: ") + hipGetErrorString(e)));
         A.S.texs = d_tx;
     }
+    if (S.env.n > 0) {   // the padded octahedral map and its descriptor (KArgs::env)
+        const size_t texels = (size_t)(S.env.n + 2) * (size_t)(S.env.n + 2);
+        if (S.env.rgba.size() != 4 * texels) return bail(pt::fail(PT_ERR_ARG, "environment map of the wrong size"));
+        v4f* d_env;
+        if (int rc = c->alloc(&d_env, texels)) return bail(rc);
+        if ((e = hipMemcpy(d_env, S.env.rgba.data(), texels * sizeof(v4f), hipMemcpyHostToDevice)) != hipSuccess)
+            return bail(pt::fail(PT_ERR_HIP, std::string("environment upload: ") + hipGetErrorString(e)));
+        A.env.map = d_env;
+        A.env.n = S.env.n;
+        A.env.scale = S.env.params.scale;
+        for (int k = 0; k < 9; ++k) A.env.rot[k] = S.env.rot[k];
+    }
 
     // ---- camera / tile ----
     const pt_camera& cam = S.camera;
@@ -4353,7 +4411,7 @@ int pt_create(const pt_scene* scene, const pt_flags* flags, const pt_shard* shar
     for (int f = 0; f < 2; ++f) {   // k_bounce: any grid is correct; one full wave of equal-work
         int per_cu = 0;              // workgroups avoids a half-empty second wave
         const int mm = A.S.ntris > 0 ? kMeshPre : 0;   // (any grid is correct for either mesh mode)
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bounce_kernel(f, sh.spp == 1, mm, false, A.S.nmats > kLdsMats || A.S.ngeoms > kLdsGeoms), kBlock,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bounce_kernel(f, sh.spp == 1, mm, false, A.S.nmats > kLdsMats || A.S.ngeoms > kLdsGeoms, A.env.map != nullptr), kBlock,
                                                          bounce_lds_bytes(A.S, mm)) != hipSuccess || per_cu <= 0)
             per_cu = 4;
         // > 2 spp workgroups: the per-iteration layout of k_bounce needs grid - spp >= spp
@@ -4556,6 +4614,8 @@ int pt_set_flags(pt_ctx* c, const pt_flags* f) {
     if (!c || !f) return pt::fail(PT_ERR_ARG, "null argument");
     if (c->ad && !c->fused && !f->sort_by_material)
         return pt::fail(PT_ERR_ARG, "an adaptive context cannot go to the split pipeline (pt_adaptive_enable)");
+    if (c->args.env.map && f->sort_by_material)
+        return pt::fail(PT_ERR_ARG, "a context with an environment cannot use material-sorted shading (sort_by_material)");
     auto same = [](float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; };
     const bool lens = !same(f->aperture, c->flags.aperture);
     const bool rays = lens || f->ssaa != c->flags.ssaa || f->dof != c->flags.dof ||
@@ -5202,6 +5262,9 @@ int pt::adaptive_quiesce(pt_ctx* c) {
 }
 
 const char* pt::adaptive_refusal(const pt_ctx* c) {
+    if (c->args.env.map)
+        return "adaptive sampling with an environment (its block masks are camera masks, which a context with an "
+               "environment does not build)";
     if (!c->args.cmask)
         return "adaptive sampling needs first-bounce camera masks (an analytic scene of at most 32 geoms without triangles, "
                "PT_AMD_NO_CMASK unset)";

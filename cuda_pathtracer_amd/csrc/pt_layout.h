@@ -170,4 +170,18 @@ struct TileDev {
 };
 static_assert(sizeof(CamDev) == 64 && sizeof(FlagsDev) == 48 && sizeof(TileDev) == 40, "kernel-argument blocks");
 
+// The environment: an octahedral radiance map, y up, of n x n RGBA32F texels inside a
+// one-texel gutter, so (n + 2)^2 float4 in all, row-major with row stride n + 2; interior texel (i, j)
+// (column along x, row along z) sits at (j + 1) * (n + 2) + (i + 1).  The gutter holds the texels bilinear
+// interpolation meets across the fold (pt_env.cpp fill_gutter), so the lookup (pt_env_dev.h) has no edge
+// case.  rot is the row-major world-to-map rotation; map == null: no environment.
+struct EnvDev {
+    const v4f* map;
+    int32_t n;
+    float scale;
+    float rot[9];
+    int32_t pad_;
+};
+static_assert(sizeof(EnvDev) == 56 && alignof(EnvDev) == 8, "kernel-argument block of the environment");
+
 }  // namespace ptd

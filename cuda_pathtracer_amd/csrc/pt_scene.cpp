@@ -344,6 +344,21 @@ static int load_json(Scene& S, const std::string& path, uint32_t options) {
         read3(cam["LOOKAT"], S.look_at);
         read3(cam["UP"], S.up);
         S.camera_set = true;
+        // Extension: "Extensions": {"ENVIRONMENT": {"FILE": .., "SCALE": .., "ROTATE": [..], "SIZE": ..}},
+        // FILE beside the textures; the reference loader ignores the key
+        if (root.has("Extensions") && root["Extensions"].kind == jl::Value::Object && root["Extensions"].has("ENVIRONMENT")) {
+            const jl::Value& ev = root["Extensions"]["ENVIRONMENT"];
+            pt_env_params prm;
+            pt_env_params_default(&prm);
+            if (ev.has("SCALE")) prm.scale = (float)ev["SCALE"].number();
+            if (ev.has("ROTATE")) read3(ev["ROTATE"], prm.rotate_deg);
+            if (ev.has("SIZE")) {
+                const double sz = ev["SIZE"].number();   // (checked as a double: the conversion of a value out of int's range is undefined)
+                if (!(sz >= 0.0 && sz <= 4096.0)) return fail(PT_ERR_PARSE, "scene: ENVIRONMENT SIZE must be 0 (default) or in 1..4096");
+                prm.size = (int32_t)sz;
+            }
+            if (int rc = load_environment_file(S, dir + "/Textures/" + ev["FILE"].string(), &prm)) return rc;
+        }
     } catch (const std::exception& e) {
         return fail(PT_ERR_PARSE, std::string("scene: ") + e.what());
     }

@@ -6,6 +6,9 @@
 //   pathtracer_amd SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise]
 //                  [--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png]
 //                  [--device-hdr] [--tonemap none|reinhard|aces|hable] [--exposure EV|auto] [--srgb] [--exr] [--exr-half]
+//                  [--env FILE.hdr] [--env-scale X] [--env-rotate X,Y,Z]
+// --env gives the scene an environment (pt_scene_load_environment of a lat-long Radiance file; --env-scale
+// multiplies its radiance, --env-rotate turns it by degrees about x, y, z); a scene file's own Extensions.ENVIRONMENT is replaced.
 // --exr additionally writes ...samp.exr, an OpenEXR file written on the device (pt_preview_exr, DESIGN.md §18: FLOAT, ZIP,
 // x-mirrored like every saved image) with the beauty layer R, G, B and, with --aov DIR, the six first-hit layers beside
 // it in the same file; --exr-half stores the layers that may be HALF as HALF.  The other files keep their names and bytes.
@@ -292,7 +295,8 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         std::printf("Usage: %s SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise] "
                     "[--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png] [--device-hdr] "
-                    "[--tonemap none|reinhard|aces|hable] [--exposure EV|auto] [--srgb] [--exr] [--exr-half]\n", argv[0]);
+                    "[--tonemap none|reinhard|aces|hable] [--exposure EV|auto] [--srgb] [--exr] [--exr-half] "
+                    "[--env FILE.hdr] [--env-scale X] [--env-rotate X,Y,Z]\n", argv[0]);
         return 1;
     }
     const char* sceneFile = argv[1];
@@ -306,6 +310,9 @@ int main(int argc, char** argv) {
     pt_display_params dprm;
     pt_display_params_default(&dprm);
     dprm.mirror_x = 1;
+    const char* env_file = nullptr;   // --env: a lat-long Radiance .hdr file as the scene's environment (pt_scene_load_environment)
+    pt_env_params eprm;
+    pt_env_params_default(&eprm);
     for (int i = 2; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--iterations") && i + 1 < argc) iterations = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out_dir = argv[++i];
@@ -321,6 +328,15 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--aov") && i + 1 < argc) { aov_dir = argv[++i]; aov = true; }
         else if (!std::strcmp(argv[i], "--adaptive") && i + 1 < argc) { adaptive_threshold = (float)std::atof(argv[++i]); adaptive = true; }
         else if (!std::strcmp(argv[i], "--adaptive-every") && i + 1 < argc) adaptive_every = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--env") && i + 1 < argc) env_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--env-scale") && i + 1 < argc) eprm.scale = (float)std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--env-rotate") && i + 1 < argc) {
+            ++i;
+            if (std::sscanf(argv[i], "%f,%f,%f", &eprm.rotate_deg[0], &eprm.rotate_deg[1], &eprm.rotate_deg[2]) != 3) {
+                std::fprintf(stderr, "--env-rotate %s: three angles in degrees, X,Y,Z\n", argv[i]);
+                return 1;
+            }
+        }
         else if (!std::strcmp(argv[i], "--tonemap") && i + 1 < argc) {
             const char* names[4] = {"none", "reinhard", "aces", "hable"};   // PT_DISPLAY_NONE .. PT_DISPLAY_HABLE
             int k = 0;
@@ -358,6 +374,10 @@ int main(int argc, char** argv) {
     }
 
     Scene* scene = new Scene(sceneFile);
+    if (env_file && pt_scene_load_environment(scene->handle(), env_file, &eprm)) {
+        std::fprintf(stderr, "error: --env %s: %s\n", env_file, pt_last_error());
+        return EXIT_FAILURE;
+    }
     GuiDataContainer* guiData = new GuiDataContainer();
     guiData->sortbyMaterial = sort;
     InitDataContainer(guiData);

@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, DisplayParams, ExrChannel, ExrParams, HdrParams,  # noqa: F401
+from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, DisplayParams, EnvParams, ExrChannel, ExrParams, HdrParams,  # noqa: F401
                       JpegParams, PngParams, TemporalParams, check_pt, lib)
 
 SPHERE, CUBE, MESH = 0, 1, 2
@@ -85,6 +85,27 @@ def decode_jpeg(data: bytes) -> np.ndarray:
     out = np.empty((h.value, w.value, c.value), np.uint8)
     check_pt(L.pt_decode_jpeg(data, len(data), C.byref(w), C.byref(h), C.byref(c),
                               out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+def decode_hdr(data: bytes) -> np.ndarray:
+    """A Radiance .hdr file's pixels, (h, w, 3) float32 in file order, by the native reader (pt_decode_hdr)."""
+    L = lib()
+    w, h = C.c_int32(), C.c_int32()
+    check_pt(L.pt_decode_hdr(data, len(data), C.byref(w), C.byref(h), None, 0))
+    out = np.empty((h.value, w.value, 3), np.float32)
+    check_pt(L.pt_decode_hdr(data, len(data), C.byref(w), C.byref(h), out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+def env_eval(scene: "Scene", dirs) -> np.ndarray:
+    """L(d) of the scene's environment for an (n, 3) array of directions, evaluated on the device by the
+    lookup the bounce kernels call (pt_env_eval): (n, 3) float32."""
+    d = np.ascontiguousarray(dirs, np.float32)
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise ValueError("env_eval: expected an (n, 3) array")
+    out = np.empty_like(d)
+    check_pt(lib().pt_env_eval_host(scene.handle, d.shape[0], d.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
     return out
 
 
@@ -282,6 +303,50 @@ class Scene:
         return {"pairs": dict(zip(kinds, map(int, r.pairs))), "bad_tagged": dict(zip(kinds, map(int, r.bad_tagged))),
                 "bad_float": dict(zip(kinds, map(int, r.bad_float))), "rays": [int(v) for v in r.rays],
                 "skipped": [int(v) for v in r.skipped], "first": first}
+
+    # -- environment lighting --
+    @staticmethod
+    def _env_params(scale, rotate, size) -> "N.EnvParams":
+        p = N.EnvParams.default()
+        p.scale = float(scale)
+        p.rotate_deg[:] = [float(v) for v in rotate]
+        p.size = 0 if size is None else int(size)
+        return p
+
+    def set_environment(self, source, scale: float = 1.0, rotate=(0, 0, 0), size: int | None = None) -> None:
+        """The scene's environment from a lat-long image: an (h, w, 3) float array (row 0 up), or the path of
+        a Radiance .hdr file.  rotate: degrees about x, y, z; size: the octahedral map's n (default: from the
+        source height, at most 2048).  PathTracers created afterwards shade their misses with it."""
+        p = self._env_params(scale, rotate, size)
+        if isinstance(source, (str, os.PathLike)):
+            check_pt(lib().pt_scene_load_environment(self._h, os.fspath(source).encode(), C.byref(p)))
+            return
+        a = np.ascontiguousarray(source, np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("environment: expected an (h, w, 3) array")
+        check_pt(lib().pt_scene_set_environment(self._h, a.shape[1], a.shape[0], a.ctypes.data_as(C.c_void_p), C.byref(p)))
+
+    def set_environment_octa(self, texels, scale: float = 1.0, rotate=(0, 0, 0)) -> None:
+        """The environment from the octahedral map itself: an (n, n, 3) float array, row j along z, column i
+        along x, +y at the centre (no gutter)."""
+        a = np.ascontiguousarray(texels, np.float32)
+        if a.ndim != 3 or a.shape[0] != a.shape[1] or a.shape[2] != 3:
+            raise ValueError("environment: expected an (n, n, 3) array")
+        p = self._env_params(scale, rotate, None)
+        check_pt(lib().pt_scene_set_environment_octa(self._h, a.shape[0], a.ctypes.data_as(C.c_void_p), C.byref(p)))
+
+    def clear_environment(self) -> None:
+        check_pt(lib().pt_scene_clear_environment(self._h))
+
+    def environment(self) -> dict | None:
+        """None, or dict(n, scale, rotate, map): map is the padded (n + 2, n + 2, 4) float32 array the device reads."""
+        n, p = C.c_int32(), N.EnvParams()
+        check_pt(lib().pt_scene_get_environment(self._h, C.byref(n), C.byref(p), None, 0))
+        if n.value <= 0:
+            return None
+        m = np.empty((n.value + 2, n.value + 2, 4), np.float32)
+        check_pt(lib().pt_scene_get_environment(self._h, C.byref(n), C.byref(p), m.ctypes.data_as(C.c_void_p), m.size))
+        return {"n": int(n.value), "scale": float(p.scale), "rotate": tuple(float(v) for v in p.rotate_deg), "map": m}
 
     def materials(self):
         nm = self.counts()[1]

@@ -230,6 +230,9 @@ class PreviewSession:
             elif name in ("auto_exposure", "srgb"):
                 self._set_display(**{name: bool(value)})
             elif name in GENERAL_SETTINGS or name in ("SSAA", "DoF"):
+                if name == "sortbyMaterial" and value and self.scene.environment() is not None:
+                    # (pt_set_flags would refuse it inside the render loop and end the session: refused here instead)
+                    raise ValueError("sortbyMaterial: a scene with an environment renders with the fused pipeline only")
                 setattr(self.gui, name, bool(value))
             elif name in SLIDERS:
                 lo, hi = SLIDERS[name]
@@ -712,6 +715,17 @@ class PreviewServer:
             pass
 
 
+def parse_rotate(text: str) -> tuple[float, float, float]:
+    """--env-rotate's X,Y,Z."""
+    parts = text.split(",")
+    if len(parts) != 3:
+        raise SystemExit(f"--env-rotate {text}: three angles in degrees, X,Y,Z")
+    try:
+        return tuple(float(v) for v in parts)
+    except ValueError:
+        raise SystemExit(f"--env-rotate {text}: three angles in degrees, X,Y,Z") from None
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description="Interactive preview of a scene (the reference's window, served as a web page)")
     ap.add_argument("scene")
@@ -722,8 +736,13 @@ def main(argv=None) -> int:
                     help="encode the frames as JPEG on the device (1..100); adds /frame.jpg and /stream.mjpg")
     ap.add_argument("--png-device", action="store_true",
                     help="write /frame.png on the device (pt_preview_png) instead of compressing the frame on the host")
+    ap.add_argument("--env", default=None, metavar="FILE", help="a lat-long Radiance .hdr file as the scene's environment")
+    ap.add_argument("--env-scale", type=float, default=1.0, metavar="X", help="multiplies the environment's radiance")
+    ap.add_argument("--env-rotate", default="0,0,0", metavar="X,Y,Z", help="the environment's rotation in degrees")
     a = ap.parse_args(argv)
     scene = Scene(a.scene)
+    if a.env:
+        scene.set_environment(a.env, scale=a.env_scale, rotate=parse_rotate(a.env_rotate))
     print(f"Reading scene from {a.scene} ...", flush=True)
     srv = PreviewServer(PreviewSession(scene, out_dir=a.out_dir, jpeg=a.jpeg, png_device=a.png_device), a.host, a.port).start()
     print(f"preview at {srv.url}  (Esc in the page saves and quits)", flush=True)

@@ -214,6 +214,46 @@ int pt_scene_get_render(const pt_scene* s, int32_t* iterations, int32_t* depth, 
  * pathtraceInit at iteration 0).  Both need a finalized scene (PT_ERR_ARG otherwise). */
 int pt_scene_get_orbit(const pt_scene* s, float* phi, float* theta, float* zoom);
 int pt_scene_set_orbit(pt_scene* s, float phi, float theta, float zoom, const float look_at[3]);
+/* ---- Environment lighting (extension) -------------------------------------------
+ * Without an environment a ray that leaves the scene is worth 0, as in the reference.  With one, it ends
+ * the path with throughput x L(direction): L is a bilinear lookup in an octahedral map (y up) of n x n
+ * RGBA32F texels, rotated by rotate_deg (Rx Ry Rz, degrees, world to map) and multiplied by scale.  No
+ * light sampling: the estimator stays the reference's.  Contexts created AFTER the call render it (fused
+ * pipeline only: pt_create / pt_set_flags refuse material-sorted shading and PT_PIPELINE=split, and
+ * pt_adaptive_enable refuses the context, each with PT_ERR_ARG); such a context builds no camera masks.
+ *   size: the map's n, 1..4096, or 0 for the default (source height / 2, at least 1, at most 2048).
+ * pt_scene_set_environment resamples a lat-long image (row 0 = +y, column centre u = 0.5 = -z, u grows
+ * towards +x; rgb = width * height * 3 floats) onto the map; a source denser than the map is box-filtered
+ * first.  pt_scene_set_environment_octa takes the n x n x 3 texels themselves (row j along z, column i
+ * along x, no gutter; params->size is ignored).  pt_scene_load_environment reads a Radiance .hdr file.
+ * pt_scene_get_environment: *n (0: none), the parameters, and the padded map, (n + 2)^2 * 4 floats, when
+ * rgba_padded is not NULL (cap floats available; PT_ERR_ARG if too few).
+ * JSON scenes: "Extensions": {"ENVIRONMENT": {"FILE": name, "SCALE": x, "ROTATE": [x, y, z], "SIZE": n}},
+ * FILE relative to <scene dir>/Textures/. */
+typedef struct pt_env_params {
+    float scale;           /* default 1 */
+    float rotate_deg[3];   /* default 0, 0, 0 */
+    int32_t size;          /* default 0: derived from the source */
+} pt_env_params;
+void pt_env_params_default(pt_env_params* p);
+int pt_scene_set_environment(pt_scene* s, int32_t width, int32_t height, const float* rgb_latlong,
+                             const pt_env_params* params);
+int pt_scene_set_environment_octa(pt_scene* s, int32_t n, const float* rgb, const pt_env_params* params);
+int pt_scene_load_environment(pt_scene* s, const char* path, const pt_env_params* params);
+int pt_scene_clear_environment(pt_scene* s);
+int pt_scene_get_environment(const pt_scene* s, int32_t* n, pt_env_params* out, float* rgba_padded, int64_t cap);
+/* Radiance HDR reader: "-Y H +X W" files of FORMAT=32-bit_rle_rgbe, new-style run-length coded or flat
+ * scanlines.  out = NULL: the size only; else height * width * 3 floats in file order (cap floats
+ * available), each mantissa byte m with exponent byte e standing for m * 2^(e - 136), 0 when e = 0.
+ * Truncated or malformed input is PT_ERR_PARSE; nothing is read beyond data[size). */
+int pt_decode_hdr(const uint8_t* data, int64_t size, int32_t* width, int32_t* height, float* out, int64_t cap);
+/* L(d) of the scene's environment for n directions (3 floats each, any length), by the lookup the bounce
+ * kernels call: d_dirs / d_rgb are device pointers (n * 3 floats); the map is uploaded for the call, the
+ * kernel runs on `stream`, and the call returns when it has completed.  pt_env_eval_host takes host
+ * pointers.  PT_ERR_ARG for a scene without an environment. */
+int pt_env_eval(const pt_scene* s, int64_t n, const float* d_dirs, float* d_rgb, void* stream);
+int pt_env_eval_host(const pt_scene* s, int64_t n, const float* dirs, float* rgb);
+
 /* Getters copy min(count, cap) records and return that number (>= 0), or -PT_ERR_ARG. */
 int pt_scene_get_geoms(const pt_scene* s, pt_geom* out, int32_t cap);
 int pt_scene_get_materials(const pt_scene* s, pt_material* out, int32_t cap);
