@@ -338,6 +338,8 @@ SIGNATURES = {
     "pt_profile_enable": (_I, [_P, _I]),
     "pt_selftest_math": (_I, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     "pt_selftest_exact": (_I, [C.c_uint64, C.c_uint32] + [C.POINTER(C.c_uint64)] * 3),
+    "pt_selftest_renorm": (_I, [C.c_uint32, C.c_uint32] + [C.POINTER(C.c_uint64)] * 3),
+    "pt_unit_rnorm_host": (_I, [_P, C.c_int64, _P, _P]),
     "pt_selftest_bounds": (_I, [_P, C.POINTER(Flags), C.c_uint64, C.c_uint32, C.POINTER(BoundsReport)]),
     "pt_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "pt_profile_read_busy": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
@@ -484,6 +486,7 @@ def _preload_torch() -> None:
 # pt_ctx_depart_counts: the A/B against the build before the room's departure claim;
 # pt_ctx_exact_counts, pt_selftest_exact: the A/B against the build before the exact tests' single gate;
 # pt_scene_bound_info, pt_selftest_bounds: the A/B against the build before the per-pair bound check;
+# pt_selftest_renorm, pt_unit_rnorm_host: the A/B against the build before the unit renormalisation;
 # pt_jpeg_*, pt_preview_jpeg: the A/B against the build before the JPEG encoder; pt_png_*, pt_preview_png: the
 # A/B against the build before the PNG encoder; pt_hdr_*, pt_preview_hdr: the A/B against the build before the
 # HDR encoder; pt_exr_*, pt_preview_exr: the A/B against the build before the OpenEXR encoder; pt_display_*, pt_preview_display: scripts/display_time.py's A/B against the build before the display
@@ -492,7 +495,7 @@ _OPTIONAL = {"pt_env_params_default", "pt_scene_set_environment", "pt_scene_set_
              "pt_scene_load_environment", "pt_scene_clear_environment", "pt_scene_get_environment", "pt_decode_hdr",
              "pt_env_eval", "pt_env_eval_host",
              "pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
-             "pt_ctx_exact_counts", "pt_selftest_exact", "pt_scene_bound_info", "pt_selftest_bounds",
+             "pt_ctx_exact_counts", "pt_selftest_exact", "pt_scene_bound_info", "pt_selftest_bounds", "pt_selftest_renorm", "pt_unit_rnorm_host",
              "pt_moments_create",
              "pt_moments_destroy", "pt_moments_reset", "pt_moments_update", "pt_moments_info", "pt_moments_variance",
              "pt_moments_get", "pt_denoise_var_params_default", "pt_denoiser_run_var", "pt_denoise_var_host",

@@ -35,7 +35,7 @@ DEVICE_SRCS = ["sc_kernels.hip", "sc_variants.hip", "pt_kernels.hip", "bvh_build
 # measured 30.8k vs 32.7k Mray/s on the bench (same box, alternating runs; same bits).
 EXTRA = {"pt_kernels.hip": ["-fno-slp-vectorize"]}
 HOST_SRCS = ["pt_scene.cpp", "pt_mesh.cpp", "pt_image.cpp", "pt_jpeg.cpp", "pt_bounds.cpp", "pt_bvh_layout.cpp",
-             "pt_ctx_image.cpp", "pt_env.cpp"]
+             "pt_ctx_image.cpp", "pt_env.cpp", "pt_renorm.cpp"]
 
 
 def other_objs(without: str) -> list[Path]:

@@ -99,6 +99,39 @@ __device__ __forceinline__ f3 norm_core(f3 v, float x) {
     return v * div_core(1.0f, s, recip_core(s));
 }
 
+// ---- renormalising a vector that is already of unit length ----------------------------------
+// getPointOnRay normalizes a direction that a normalize, a reflection or a hemisphere sample has just
+// produced: x = dot(v, v) is within a few ulp of 1.  For x in [1 - 2^-12, 1 + 2^-12] the factor
+// 1 / sqrt(x) of norm_core, both roundings included, is a function of x's signed distance from 1.0f
+// in ulps, k = bits(x) - bits(1.0f) (one ulp is 2^-23 above 1 and 2^-24 below; k in [-4096, 2048]):
+//   k >= 0:  sqrt(1 + k 2^-23) = 1 + (k/2) 2^-23 - (k^2/8) 2^-46 + ...: below 1 + (k/2) 2^-23 by less
+//            than 2^-4 ulp, so it rounds to s = 1 + m 2^-23 with m = floor(k/2) (an odd k lies just
+//            under the midpoint).  1 / s = 1 - 2m 2^-24 + m^2 2^-46 - ...: above 1 - 2m 2^-24 by at
+//            most 2^-2 ulp (of 2^-24), so it rounds to it:            bits = bits(1) - (k & ~1);
+//   k < 0:   with j = -k, sqrt(1 - j 2^-24) = 1 - (j/2) 2^-24 - (j^2/8) 2^-48 - ...: rounds to
+//            s = 1 - m 2^-24 with m = ceil(j/2) (an odd j lies just beyond the midpoint).
+//            1 / s = 1 + (m/2) 2^-23 + (m^2/2) 2^-47 + ...: above 1 + (m/2) 2^-23 by at most 2^-3 ulp,
+//            so it rounds to 1 + ceil(m/2) 2^-23 = 1 + ceil(j/4) 2^-23:  bits = bits(1) + ((j + 3) >> 2).
+// The argument is a guide only.  The proof is exhaustive: tests/test_renorm_unit_cpu.py compares the
+// host restatement of unit_rnorm (pt_renorm.cpp) with the correctly rounded 1.0f / sqrtf(x) for every
+// one of the 6,145 floats of the range, and tests/test_renorm_unit_gpu.py compares renorm_unit_core
+// with norm_core on the device for the same values.  sqrt_core and div_core are correctly rounded on
+// the whole range (pt_selftest_math), so the three agree.
+// (unit_ok_bits, unit_rnorm_bits: pt_layout.h, shared with the host's restatement.)
+__device__ __forceinline__ bool unit_ok(float x) { return unit_ok_bits(__float_as_uint(x)); }
+// 1 / sqrt(x) as norm_core rounds it, for unit_ok(x)
+__device__ __forceinline__ float unit_rnorm(float x) { return __uint_as_float(unit_rnorm_bits(__float_as_uint(x))); }
+// norm_core(v, x), bit for bit, for every x: the closed form in range, norm_core's own operations
+// behind a branch (cold where v is a unit vector) for every other x, zero, infinite and NaN included.
+__device__ __forceinline__ f3 renorm_unit_core(f3 v, float x) {
+    float inv = unit_rnorm(x);
+    if (__builtin_expect(!unit_ok(x), 0)) {
+        const float s = sqrt_core(x);
+        inv = div_core(1.0f, s, recip_core(s));
+    }
+    return v * inv;
+}
+
 // ---- one range gate for a whole exact test (pt_kernels.hip exact_geom) --------
 // The per-operation forms above pay a compare, an exec-mask region and a branch for each sqrt,
 // division and normalize.  A fast path runs the cores unconditionally and feeds every gated operand
@@ -132,6 +165,12 @@ struct RangeGate {
         const uint32_t u = __float_as_uint(x);
         mn = min(mn, u + (56u << 23));
         mx = max(mx, __builtin_elementwise_sub_sat(u, 0x7f7fffffu - kHi));
+    }
+    // unit(x): unit_ok(x) <=> w = bits(x) - bits(1 - 2^-12) <= kUnitSpan (unsigned: a smaller x wraps to a
+    // large w).  mx takes the saturating w + (kHi - kUnitSpan): <= kHi iff w <= kUnitSpan, and no wrap.
+    __device__ __forceinline__ void unit(float x) {
+        const uint32_t w = __float_as_uint(x) - (kUnitBits - kUnitBelow);
+        mx = max(mx, __builtin_elementwise_add_sat(w, kHi - kUnitSpan));
     }
     __device__ __forceinline__ bool ok() const { return mn >= kLo && mx <= kHi; }
 };
@@ -207,5 +246,17 @@ __device__ __forceinline__ void sincos_c(float x, float* s_out, float* c_out) {
 
 // getPointOnRay (intersections.h:29-32)
 __device__ __forceinline__ f3 point_on_ray(f3 o, f3 d, float t) { return o + (t - .0001f) * normalize(d); }
+// point_on_ray for a direction that is a unit vector in all ordinary use (shade's path: a camera ray, a
+// reflection, a hemisphere sample): the same bits for every d, normalize's own code behind one cold branch.
+__device__ __forceinline__ f3 point_on_ray_unit(f3 o, f3 d, float t) {
+    const float x = dot(d, d);
+    float inv = unit_rnorm(x);
+    if (__builtin_expect(!unit_ok(x), 0)) {
+        const float s = sqrt_core(x);
+        inv = div_core(1.0f, s, recip_core(s));
+        if (__builtin_expect(!(x >= 0x1p-80f && x <= 0x1p+80f), 0)) inv = 1.0f / sqrtf(x);
+    }
+    return o + (t - .0001f) * (d * inv);
+}
 
 }  // namespace ptd

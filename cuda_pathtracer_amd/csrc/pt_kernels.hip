@@ -42,6 +42,12 @@
 
 using namespace ptd;
 
+// Measurement switch (scripts/build_variants.sh; never set in the product): bit 0 keeps the root and the
+// reciprocal in exact_geom's point_on_ray, bit 1 in shade's.  Same bits either way.
+#ifndef PT_RENORM_OFF
+#define PT_RENORM_OFF 0
+#endif
+
 namespace {
 
 constexpr int kBlock = 256;
@@ -918,7 +924,9 @@ __device__ __forceinline__ float exact_geom_literal(const LGeom& L, f3 r_o, f3 r
 //    normal, so no component of qd = qv * (1 / s) is a NaN.  Each is qv_k / |qv| within a few 2^-23
 //    relative (products below 2^-126 that underflow in qq are below 2^-46 of it), so |qd_k| <= 1 + 2^-20
 //    and dot(qd, qd) is within 2^-20 of 1: the radicand of point_on_ray's normalize always passes
-//    its range test and is not fed to the gate.
+//    normalize's range test.  It also lies in [1 - 2^-12, 1 + 2^-12], where 1 / sqrt, both roundings
+//    included, is the closed form unit_rnorm (pt_device.h) instead of a root and a reciprocal.  That
+//    range is fed to the gate (RangeGate::unit) all the same, so the form never rests on this argument.
 //  - Cube.  With |n|, |d| in [2^-40, 2^40] every slab parameter t1, t2 is a correctly rounded quotient
 //    with magnitude in [2^-80, 2^80]: finite, not NaN, not zero.  On such values
 //      a < b ? a : b == fminf(a, b) and a > b ? a : b == fmaxf(a, b)  (no NaN to order, no +-0 pair to
@@ -1000,7 +1008,14 @@ __device__ __forceinline__ float exact_geom(const LGeom& L, f3 r_o, f3 r_d, int&
     }
     float res = -1.0f;
     if (hit) {
-        obj = qo + (t - .0001f) * norm_core(qd, dot(qd, qd));   // point_on_ray: its radicand needs no test (above)
+        // point_on_ray: qd is a unit vector, so its normalize takes the closed form of renorm_unit_core
+        const float q1 = dot(qd, qd);
+#if PT_RENORM_OFF & 1   // measurement: the root and the reciprocal as before (profiles/r11_valu_overhead_ab.txt)
+        obj = qo + (t - .0001f) * norm_core(qd, q1);
+#else
+        gate.unit(q1);
+        obj = qo + (t - .0001f) * (qd * unit_rnorm(q1));
+#endif
         const f3 w = r_o - xform_point(L.xf, obj);
         const float ww = dot(w, w);
         gate.root(ww);
@@ -1408,7 +1423,11 @@ template <bool ENV = false, class MT>
 __device__ __forceinline__ bool shade(const SceneDev& S, const FlagsDev& fl, int depth, int iter, int idx,
                                       PathReg& p, const Hit& h, const MT* mats, const float* frames = nullptr) {
     if (shade_ends<ENV>(h, mats, p)) return false;
+#if PT_RENORM_OFF & 2   // measurement, as in exact_geom
     return shade_from(S, fl, depth, iter, idx, p, h, point_on_ray(p.o, p.d, h.t), mats, frames);
+#else
+    return shade_from(S, fl, depth, iter, idx, p, h, point_on_ray_unit(p.o, p.d, h.t), mats, frames);
+#endif
 }
 
 // generateRayFromCamera (pathtrace.cu:183-227) for tile slot `slot`.
@@ -3223,7 +3242,11 @@ void k_sort_produce(const KArgs A, const SortArgs SA) {
                 v4f* r = srec(A.out, q);
                 // (plain stores: each store instruction covers 16 of every 32 bytes, and L2 merges the
                 // two into whole lines; non-temporal ones halved config 3's rate)
+#if PT_RENORM_OFF & 2
                 const f3 hitp = point_on_ray(p.o, p.d, h.t);
+#else
+                const f3 hitp = point_on_ray_unit(p.o, p.d, h.t);
+#endif
                 const int code = h.frame >= 0 ? h.frame : -(h.mat + 1);
                 r[0] = v4f{hitp.x, hitp.y, hitp.z, p.c.x};
                 r[1] = v4f{p.c.y, p.c.z, __int_as_float(p.slot), __int_as_float(rec_pack(code, kb))};
@@ -3503,6 +3526,47 @@ __global__ void k_selftest_math(uint64_t n, uint32_t seed, unsigned long long* b
         e += same_bits(length(v), sqrtf(dot(v, v))) ? 0 : 1;
     }
     if (e) atomicAdd(bad, e);
+}
+
+// pt_selftest_renorm: renorm_unit_core against norm_core, and point_on_ray_unit against point_on_ray.
+// Item i: below kUnitSpan + 1 — the floats of [1 - 2^-12, 1 + 2^-12], every one, as x with a fixed vector;
+// the next 16 — the first float outside on each side and edge values of x (they must take the general
+// path); the next nvec — vectors from `seed` with x = dot(v, v): three of four normalized (in range),
+// the fourth as drawn (length up to 1.7, or a pt_selftest_math operand).  out[0] mismatches, out[1] items
+// that passed unit_ok, out[2] items whose unit_ok differs from the range stated here.
+__global__ void k_selftest_renorm(uint32_t nvec, uint32_t seed, unsigned long long* out) {
+    constexpr uint32_t nx = kUnitSpan + 1u, nedge = 16u, lo = kUnitBits - kUnitBelow;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nx + nedge + nvec) return;
+    f3 v = F3(0.6f, -0.48f, 0.64f);
+    float x;
+    if (i < nx) {
+        x = __uint_as_float(lo + i);
+    } else if (i < nx + nedge) {
+        const float e[nedge] = {__uint_as_float(lo - 1u), __uint_as_float(lo + nx), 0.0f, -0.0f, 1e-45f, 0x1p-100f,
+                                0x1p+100f, 3.402823466e+38f, __builtin_inff(), -__builtin_inff(), __builtin_nanf(""),
+                                -1.0f, 0.5f, 2.0f, 0x1p-126f, -__builtin_nanf("")};
+        x = e[i - nx];
+    } else {
+        uint32_t h = utilhash(i ^ seed);
+        auto next = [&]() { h = utilhash(h + 0x7f4a7c15u); return h; };
+        auto uni = [&]() { return (float)(next() >> 8) * 0x1p-23f - 1.0f; };
+        v = F3(uni(), uni(), uni());
+        if ((i & 3u) != 3u) v = normalize(v);
+        else if ((i & 12u) == 12u) v.y = selftest_operand(next(), (uint64_t)i, 0);
+        x = dot(v, v);
+    }
+    const bool in = unit_ok(x), want = x >= 1.0f - 0x1p-12f && x <= 1.0f + 0x1p-12f;
+    const f3 a = renorm_unit_core(v, x), b = norm_core(v, x);
+    bool same = same_bits(a.x, b.x) && same_bits(a.y, b.y) && same_bits(a.z, b.z);
+    if (in) same = same && same_bits(unit_rnorm(x), div_core(1.0f, sqrt_core(x), recip_core(sqrt_core(x))));
+    if (i >= nx + nedge) {   // x is dot(v, v): the two forms of getPointOnRay
+        const f3 o = F3(1.25f, -3.5f, 0.75f), p = point_on_ray_unit(o, v, 2.75f), q = point_on_ray(o, v, 2.75f);
+        same = same && same_bits(p.x, q.x) && same_bits(p.y, q.y) && same_bits(p.z, q.z);
+    }
+    if (!same) atomicAdd(out + 0, 1ull);
+    if (in) atomicAdd(out + 1, 1ull);
+    if (in != want) atomicAdd(out + 2, 1ull);
 }
 
 // pt_selftest_exact: exact_geom (fast path under one gate, literal fallback) against exact_geom_literal.
@@ -5077,6 +5141,27 @@ int pt_selftest_math(uint64_t n, uint32_t seed, uint64_t* mismatches) {
     (void)hipFree(d);
     if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("selftest: ") + hipGetErrorString(e));
     *mismatches = h;
+    return PT_OK;
+}
+
+int pt_selftest_renorm(uint32_t nvec, uint32_t seed, uint64_t* mismatches, uint64_t* in_range, uint64_t* misranged) {
+    if (!mismatches || !in_range || !misranged) return pt::fail(PT_ERR_ARG, "null argument");
+    if (nvec > (1u << 24)) return pt::fail(PT_ERR_ARG, "at most 2^24 vectors");
+    unsigned long long* d = nullptr;
+    unsigned long long h[3] = {0, 0, 0};
+    HIP_TRY(hipMalloc(&d, sizeof h));
+    hipError_t e = hipMemset(d, 0, sizeof h);
+    if (e == hipSuccess) {
+        const uint32_t n = kUnitSpan + 1u + 16u + nvec;
+        hipLaunchKernelGGL(k_selftest_renorm, dim3((n + 255u) / 256u), dim3(256), 0, nullptr, nvec, seed, d);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);   // (synchronises)
+    (void)hipFree(d);
+    if (e != hipSuccess) return pt::fail(PT_ERR_HIP, std::string("selftest: ") + hipGetErrorString(e));
+    *mismatches = h[0];
+    *in_range = h[1];
+    *misranged = h[2];
     return PT_OK;
 }
 

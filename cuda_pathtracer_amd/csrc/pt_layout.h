@@ -13,6 +13,17 @@ constexpr float kSQRT_1_3 = 0.5773502691896257645091487805019574556476f; // util
 constexpr float kFLT_MAX = 3.402823466e+38f;
 constexpr float kFLT_EPS = 1.192092896e-07f;
 
+// 1 / sqrt(x) of a float x in [1 - 2^-12, 1 + 2^-12], rounded as sqrt and then as 1 / s (glm's normalize),
+// from x's bit pattern u alone: the derivation is in pt_device.h (renorm_unit_core), the exhaustive check
+// of all 6,145 values in tests/test_renorm_unit_cpu.py (through pt_renorm.cpp) and, on the device,
+// tests/test_renorm_unit_gpu.py.  constexpr: the kernels and the host compile the same lines.
+constexpr uint32_t kUnitBits = 0x3f800000u, kUnitBelow = 4096u, kUnitSpan = 6144u;   // 4096 floats below 1, 2048 above
+constexpr bool unit_ok_bits(uint32_t u) { return u - (kUnitBits - kUnitBelow) <= kUnitSpan; }
+constexpr uint32_t unit_rnorm_bits(uint32_t u) {   // meaningful when unit_ok_bits(u)
+    const uint32_t k = u - kUnitBits;   // x's signed distance from 1.0f in ulps, two's complement
+    return (int32_t)k < 0 ? kUnitBits + ((3u - k) >> 2) : kUnitBits - (k & ~1u);
+}
+
 // Affine 3x4 in glm column order + the exact glm w-term constants.
 //   point  (w=1): (c0 x + c1 y) + (c2 z + c3)
 //   vector (w=0): (c0 x + c1 y) + (c2 z + z3),  z3 = c3 * 0.0f (a signed zero)

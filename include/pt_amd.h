@@ -433,6 +433,18 @@ int pt_selftest_math(uint64_t n, uint32_t seed, uint64_t* mismatches);
  * NaN) or, for a hit, whose slab code, object-space point or side differ; *tripped = pairs whose gate
  * tripped; *fast = pairs the fast path answered.  Synchronous. */
 int pt_selftest_exact(uint64_t n, uint32_t seed, uint64_t* mismatches, uint64_t* tripped, uint64_t* fast);
+/* Device self-check of the renormalisation of unit vectors (pt_device.h renorm_unit_core, the closed form
+ * of 1 / sqrt(x) on [1 - 2^-12, 1 + 2^-12]) against the general normalize core, in one launch: every one
+ * of the 6,145 floats of that range, the first float outside on each side, zero, denormal, huge, infinite,
+ * negative and NaN x, and nvec vectors from `seed` (three of four of unit length), for which the two forms
+ * of getPointOnRay are compared as well.  *mismatches = items whose bits differ (NaN == NaN); *in_range =
+ * items that took the closed form; *misranged = items whose range test differs from the stated range.
+ * Synchronous. */
+int pt_selftest_renorm(uint32_t nvec, uint32_t seed, uint64_t* mismatches, uint64_t* in_range, uint64_t* misranged);
+/* The closed form itself on the host (no device): out[i] = the bits of 1 / sqrt(x) for the float x with
+ * bits[i] and in_range[i] = 1 where x lies in [1 - 2^-12, 1 + 2^-12]; elsewhere in_range[i] = 0 and
+ * out[i] = 0 (the kernels run the general normalize there). */
+int pt_unit_rnorm_host(const uint32_t* bits, int64_t n, uint32_t* out, uint8_t* in_range);
 /* Device self-check of the bounded closest hit's lower bounds, per (ray, geom) pair.
  * The scene is prepared as pt_create prepares it (geom table, widened bounds with the flags' aperture,
  * room, bound order) and uploaded; n rays are generated on the device from `seed`, and every ray is
