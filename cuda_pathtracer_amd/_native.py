@@ -321,6 +321,7 @@ SIGNATURES = {
     "pt_ctx_counters": (_I, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "pt_ctx_stream_info": (_I, [_P] + [C.POINTER(C.c_int32)] * 5),
     "pt_ctx_walk_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_double)]),
+    "pt_ctx_walk_kind": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "pt_render_pass": (_I, [_P, _I, _P]),
     "pt_render_ahead": (_I, [_P, _I, _P]),
     "pt_host_register": (_I, [_P, C.c_uint64]),
@@ -495,7 +496,7 @@ _OPTIONAL = {"pt_env_params_default", "pt_scene_set_environment", "pt_scene_set_
              "pt_scene_load_environment", "pt_scene_clear_environment", "pt_scene_get_environment", "pt_decode_hdr",
              "pt_env_eval", "pt_env_eval_host",
              "pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",
-             "pt_ctx_exact_counts", "pt_selftest_exact", "pt_scene_bound_info", "pt_selftest_bounds", "pt_selftest_renorm", "pt_unit_rnorm_host",
+             "pt_ctx_exact_counts", "pt_ctx_walk_kind", "pt_selftest_exact", "pt_scene_bound_info", "pt_selftest_bounds", "pt_selftest_renorm", "pt_unit_rnorm_host",
              "pt_moments_create",
              "pt_moments_destroy", "pt_moments_reset", "pt_moments_update", "pt_moments_info", "pt_moments_variance",
              "pt_moments_get", "pt_denoise_var_params_default", "pt_denoiser_run_var", "pt_denoise_var_host",

@@ -27,12 +27,24 @@ std::vector<DNode> to_dnodes(const std::vector<pt_bvh_node>& bvh) {
     return nodes;
 }
 
+// Every leaf fits the leaf code of the pair and quad layouts: count in the low 8 bits, first above them.
+bool leaf_codes_fit(const std::vector<DNode>& nodes) {
+    for (const DNode& n : nodes) {
+        const int32_t meta = __float_as_int_host(n.lo[3]), link = __float_as_int_host(n.hi[3]);
+        if (meta > 255 || (meta > 0 && (link < 0 || (int64_t)link + meta > (int64_t)1 << 23))) return false;
+    }
+    return true;
+}
+
 // The 4-wide layout (DQuad) of the flattened tree `nodes` (DNode encoding: left child = i + 1).
 // An interior child X of a quad's node is replaced by its two children when both boxes lie inside
 // X's box as floats (the nesting k_traverse4's exactness rests on); otherwise it keeps one slot.
 // Also bounds the walk's stack: per quad (valid slots - 1) pushes, summed along the worst path.
 // Leaves of zero triangles (never built by the SAH builder) or a bound beyond the stack's capacity
-// leave the quad layout off (k_traverse's pair walk runs instead).
+// leave the quad layout off (k_traverse's pair walk runs instead).  So does a leaf the leaf code cannot
+// hold, -(first * 256 + count) - 1: more than 255 triangles (a range whose centre box is degenerate is
+// one leaf, whatever its size) or a first triangle at 2^23 or beyond; no walk by codes runs then (the
+// context builds no pair layout either), only the node-at-a-time walk.
 // Host part: fills `quads`, the root's code and the stack bound; false = no quad layout.
 bool make_quads(const std::vector<DNode>& nodes, std::vector<DQuad>& quads, int32_t& root_code, int32_t& root_occ,
                 std::vector<int32_t>* slot_node) {
@@ -45,6 +57,7 @@ bool make_quads(const std::vector<DNode>& nodes, std::vector<DQuad>& quads, int3
     for (size_t i = 0; i < n; ++i)
         if (meta(i) == 0 || (meta(i) < 0 && (link(i) <= (int32_t)i + 1 || (size_t)link(i) >= n)))
             return false;   // (a zero-triangle leaf is indistinguishable here; malformed links)
+    if (!leaf_codes_fit(nodes)) return false;
     auto inside = [&](size_t in, size_t out) {
         for (int k = 0; k < 3; ++k)
             if (!(nodes[in].lo[k] >= nodes[out].lo[k] && nodes[in].hi[k] <= nodes[out].hi[k])) return false;

@@ -126,6 +126,7 @@ void camera_masks(const BoundsHost& B, const ptd::CamDev& cam, const ptd::FlagsD
 void room_info(const ptd::RoomDev& room, int32_t* walls, int32_t* faces, float* lo, float* hi);
 // BVH layouts of the walk kernels (pt_bvh_layout.cpp; no device needed)
 std::vector<ptd::DNode> to_dnodes(const std::vector<pt_bvh_node>& bvh);
+bool leaf_codes_fit(const std::vector<ptd::DNode>& nodes);   // the pair / quad layouts' leaf code holds every leaf
 bool make_quads(const std::vector<ptd::DNode>& nodes, std::vector<ptd::DQuad>& quads, int32_t& root_code,
                 int32_t& root_occ, std::vector<int32_t>* slot_node = nullptr);
 double build_qcull(const std::vector<ptd::DNode>& nodes, const std::vector<pt_triangle>& tris,

@@ -290,6 +290,14 @@ struct MeshHit {
 // entries are never reached (pt_create checks the depth: occupancy <= interior depth); deeper trees
 // use a 64-entry private array (scratch), which is the reference's exact overflow behaviour.
 constexpr int kLdsStack = 32;
+// Which walk runs for a tree, one predicate each for the kernels and pt_ctx_walk_info:
+// bvh_traverse keeps its stack in LDS (else a private 64-entry array and the node walk)
+__host__ __device__ __forceinline__ bool inline_lds_stack(int bvh_depth) { return bvh_depth < kLdsStack; }
+// k_traverse's pair walk pushes only passing children: exact while its stack never reaches the
+// reference's 64 entries (occupancy <= bvh_depth + 1); else, and under bvh_cull, the node walk
+__host__ __device__ __forceinline__ bool pair_walk_exact(bool pairs, bool cull, int bvh_depth) {
+    return pairs && !cull && bvh_depth + 2 <= 64;
+}
 
 template <class Stack>
 __device__ __forceinline__ MeshHit bvh_walk(const SceneDev& S, f3 o, f3 d, bool cull, Stack stack) {
@@ -415,7 +423,7 @@ __device__ unsigned long long g_trav[64 * 8];   // [slot][0 rays, 1 pairs, 2 tri
 
 __device__ MeshHit bvh_traverse(const SceneDev& S, f3 o, f3 d, bool cull) {
     if (S.nnodes == 0) return MeshHit{false, -1, -1, kFLT_MAX, 0.f, 0.f};
-    if (S.bvh_depth < kLdsStack) {
+    if (inline_lds_stack(S.bvh_depth)) {
         __shared__ int s_stack[kLdsStack * kBlock];
         if (S.pairs && !cull) return bvh_walk_pairs(S, o, d, LdsStack{s_stack + threadIdx.x});
         return bvh_walk(S, o, d, cull, LdsStack{s_stack + threadIdx.x});
@@ -1923,9 +1931,7 @@ __global__ __launch_bounds__(kBlock) void k_traverse(const KArgs A) {
     };
     int spill[64];   // stack entries past the LDS rows (HybStack)
     const HybStack st{s_tstack + tid, spill, A.stack_rows};
-    // the pair walk pushes only passing children: exact while its stack never reaches the reference's
-    // 64 entries (occupancy <= bvh_depth + 1); else, and under bvh_cull, the node-at-a-time walk
-    if (!(S.pairs && !A.fl.bvh_cull && S.bvh_depth + 2 <= 64)) {
+    if (!pair_walk_exact(S.pairs != nullptr, A.fl.bvh_cull != 0, S.bvh_depth)) {   // the node-at-a-time walk
         for (int k = (int)blockIdx.x * kBlock + tid; k < N; k += (int)gridDim.x * kBlock) {
             f3 o, d;
             const int q = ray(k, o, d);
@@ -4381,10 +4387,8 @@ int pt_create(const pt_scene* scene, const pt_flags* flags, const pt_shard* shar
             }
         A.S.bvh_depth = deepest;
         // child-pair layout (bvh_walk_pairs): leaves of <= 255 triangles, triangle ids < 2^23
-        bool fits = S.triangles.size() < (1u << 23);
-        for (const DNode& n : nodes)
-            if (__float_as_int_host(n.lo[3]) > 255) fits = false;
-        if (fits) {
+        // (pt::leaf_codes_fit: make_quads refuses the same trees, so pt_scene_bvh_quads agrees with this)
+        if (S.triangles.size() < (1u << 23) && pt::leaf_codes_fit(nodes)) {
             std::vector<int32_t> pid(nodes.size(), -1);
             int32_t np = 0;
             for (size_t i = 0; i < nodes.size(); ++i)
@@ -4704,6 +4708,27 @@ int pt_ctx_walk_info(const pt_ctx* c, int32_t* quad_walk, int32_t* tcull_on, dou
     if (quad_walk) *quad_walk = c->trav_quads ? 1 : 0;
     if (tcull_on) *tcull_on = c->args.S.qcull != nullptr ? 1 : 0;
     if (tcull_frac) *tcull_frac = c->tcull_frac;
+    return PT_OK;
+}
+
+int pt_ctx_walk_kind(const pt_ctx* c, int32_t* walk, int32_t* inline_walk, int32_t* bvh_depth, int32_t* stack_bound) {
+    if (!c) return pt::fail(PT_ERR_ARG, "null context");
+    const SceneDev& S = c->args.S;
+    const bool cull = c->args.fl.bvh_cull != 0;
+    if (walk) {   // launch_bounce's and k_traverse's choice under the current flags
+        *walk = PT_WALK_NONE;
+        if (mesh_mode(c) == kMeshPre && c->fused && c->flags.sort_by_material == 0)   // (render_pass's pipelines)
+            *walk = (c->trav_quads && !cull) ? PT_WALK_QUADS
+                    : pair_walk_exact(S.pairs != nullptr, cull, S.bvh_depth) ? PT_WALK_PAIRS : PT_WALK_NODES;
+    }
+    if (inline_walk) {   // bvh_traverse's choice (k_bounce's kMeshInline, the G-buffer, non-finite rays)
+        *inline_walk = PT_WALK_NONE;
+        if (S.nnodes > 0 && c->args.fl.bvh)
+            *inline_walk = !inline_lds_stack(S.bvh_depth) ? PT_WALK_NODES_PRIVATE
+                           : (S.pairs && !cull) ? PT_WALK_PAIRS : PT_WALK_NODES;
+    }
+    if (bvh_depth) *bvh_depth = S.bvh_depth;
+    if (stack_bound) *stack_bound = c->quad_occ;
     return PT_OK;
 }
 

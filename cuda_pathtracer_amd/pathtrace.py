@@ -477,7 +477,17 @@ class PathTracer:
         cull margin can pay (pt_ctx_walk_info)."""
         qw, on, fr = C.c_int32(), C.c_int32(), C.c_double()
         check_pt(lib().pt_ctx_walk_info(self._h, C.byref(qw), C.byref(on), C.byref(fr)))
-        return {"quad_walk": bool(qw.value), "tcull": bool(on.value), "tcull_frac": float(fr.value)}
+        info = {"quad_walk": bool(qw.value), "tcull": bool(on.value), "tcull_frac": float(fr.value)}
+        if hasattr(lib(), "pt_ctx_walk_kind"):
+            # walk: the kernel ahead of the bounce kernel ("quads", "pairs", "nodes"; "none": inside it);
+            # inline_walk: the walk inside the bounce kernel and of the G-buffer ("pairs", "nodes",
+            # "nodes_private": the reference's 64 private entries; "none": no tree, or the BVH flag off)
+            names = ("none", "quads", "pairs", "nodes", "nodes_private")
+            w, iw, dp, sb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+            check_pt(lib().pt_ctx_walk_kind(self._h, C.byref(w), C.byref(iw), C.byref(dp), C.byref(sb)))
+            info.update(walk=names[w.value], inline_walk=names[iw.value], bvh_depth=int(dp.value),
+                        stack_bound=int(sb.value))
+        return info
 
     def render_pass(self, iter_first: int, stream=None) -> None:
         """pathtrace(): iterations [iter_first, iter_first + spp) for this tile, asynchronous."""

@@ -333,6 +333,18 @@ int pt_ctx_exact_counts(pt_ctx* c, uint64_t* tests, uint64_t* tripped);
  * the share of the layout's slots whose cull margin can pay.  The cull is on when
  * that share is >= 1/4 (PT_AMD_TCULL=0/1 forces it); it never changes a result. */
 int pt_ctx_walk_info(const pt_ctx* c, int32_t* quad_walk, int32_t* tcull_on, double* tcull_frac);
+/* Mesh scenes, read-only: which BVH walk the context runs under its current flags, as the kernels
+ * themselves decide it (the same predicates).  walk — the walk launched ahead of the bounce kernel:
+ * PT_WALK_QUADS (k_traverse4), PT_WALK_PAIRS or PT_WALK_NODES (k_traverse's two forms), PT_WALK_NONE
+ * when the walk runs inside the bounce kernel (PT_AMD_MESH_INLINE=1, the material-sorted and the split
+ * pipeline, more geoms than the LDS table holds).  inline_walk — the walk of that inline form, of the
+ * G-buffer and of the rays the 4-wide walk leaves to the bounce kernel: PT_WALK_PAIRS, PT_WALK_NODES
+ * (both with the stack in LDS), PT_WALK_NODES_PRIVATE (a tree of depth >= 32: the reference's 64
+ * private entries), PT_WALK_NONE without a tree or with the BVH flag off.  bvh_depth — the depth of
+ * the deepest interior node; stack_bound — the 4-wide layout's bound on its stack (0 without one).
+ * Any pointer may be null. */
+enum { PT_WALK_NONE = 0, PT_WALK_QUADS = 1, PT_WALK_PAIRS = 2, PT_WALK_NODES = 3, PT_WALK_NODES_PRIVATE = 4 };
+int pt_ctx_walk_kind(const pt_ctx* c, int32_t* walk, int32_t* inline_walk, int32_t* bvh_depth, int32_t* stack_bound);
 /* Stream budget.  HIP maps a process's streams of one priority onto GPU_MAX_HW_QUEUES (default 4)
  * hardware queues; streams beyond that share queues and their work runs in submission order.  A
  * context keeps busy: the caller's stream, one stream per extra lane of a batched pass, and the

@@ -60,11 +60,18 @@ def _slab(bmin, bmax, o, inv, finite):
     return not (hi < 0) and not (lo > hi)
 
 
-def _walk_binary(pn, o, d):
-    """The reference's walk: leaves reached, in order, as (first triangle, count)."""
+def _walk_binary(pn, o, d, overflow="assert", stats=None):
+    """The reference's walk: leaves reached, in order, as (first triangle, count).
+    overflow: what an interior node does when the stack already holds 64 entries — "assert": that never
+    happens (the trees of this file); "reference": intersections.cu:202-205, the node is skipped (its
+    whole subtree is dropped) and the walk goes on with the popped entry; "none": the stack just grows
+    (what the reference does NOT do; for tests that show the rule's effect).  stats: a dict that gets
+    the deepest occupancy reached ("deepest") and the number of skipped nodes ("skipped")."""
+    assert overflow in ("assert", "reference", "none")
     inv = (f32(1) / d).astype(f32)
     neg = d < 0
     out, stack, cur = [], [], 0
+    deepest = skipped = 0
     while True:
         n = pn[cur]
         if _slab(n["bmin"], n["bmax"], o, inv, False):
@@ -74,17 +81,26 @@ def _walk_binary(pn, o, d):
                     break
                 cur = stack.pop()
             else:
-                assert len(stack) < 64
+                if overflow == "assert":
+                    assert len(stack) < 64
+                elif overflow == "reference" and len(stack) == 64:
+                    skipped += 1
+                    cur = stack.pop()
+                    continue
                 if neg[n["axis"]]:
                     stack.append(cur + 1)
                     cur = int(n["rchild_idx"])
                 else:
                     stack.append(int(n["rchild_idx"]))
                     cur = cur + 1
+                deepest = max(deepest, len(stack))
         else:
             if not stack:
                 break
             cur = stack.pop()
+    if stats is not None:
+        stats["deepest"] = max(stats.get("deepest", 0), deepest)
+        stats["skipped"] = stats.get("skipped", 0) + skipped
     return out
 
 
