@@ -12,7 +12,7 @@ from .pathtrace import (  # noqa: F401
     DenoiseVarParams, denoise_variance, TemporalParams, TemporalHistory, AdaptiveParams, JpegParams, JpegEncoder, encode_jpeg,
     PngParams, PngEncoder, encode_png, HdrParams, HdrEncoder, encode_hdr_device, DisplayParams, DisplayTransform,
     display_transform, display_tables, ExrParams, ExrChannel, ExrEncoder, encode_exr, exr_ctx_channels, EnvParams,
-    decode_hdr, env_eval)
+    decode_hdr, env_eval, BloomParams, Bloom, bloom)
 from ._native import (  # noqa: F401
     EXR_UINT, EXR_HALF, EXR_FLOAT, EXR_NONE, EXR_ZIPS, EXR_ZIP, EXR_BEAUTY, EXR_ALBEDO, EXR_NORMAL, EXR_POSITION, EXR_DEPTH,
     EXR_UV, EXR_ID, EXR_ALL_LAYERS)
@@ -29,4 +29,4 @@ __all__ = ["Scene", "PathTracer", "GuiDataContainer", "Efficient", "CPU", "Naive
            "HdrParams", "HdrEncoder", "encode_hdr_device", "DisplayParams", "DisplayTransform", "display_transform",
            "display_tables", "ExrParams", "ExrChannel", "ExrEncoder", "encode_exr", "exr_ctx_channels", "EXR_UINT", "EXR_HALF",
            "EXR_FLOAT", "EXR_NONE", "EXR_ZIPS", "EXR_ZIP", "EXR_BEAUTY", "EXR_ALBEDO", "EXR_NORMAL", "EXR_POSITION", "EXR_DEPTH",
-           "EXR_UV", "EXR_ID", "EXR_ALL_LAYERS", "EnvParams", "decode_hdr", "env_eval", "lib", "LIB_PATH", "NativeLibraryError", "PtError"]
+           "EXR_UV", "EXR_ID", "EXR_ALL_LAYERS", "EnvParams", "decode_hdr", "env_eval", "BloomParams", "Bloom", "bloom", "lib", "LIB_PATH", "NativeLibraryError", "PtError"]

@@ -243,9 +243,22 @@ class EnvParams(C.Structure):
 
 assert C.sizeof(EnvParams) == 20
 DISPLAY_MANUAL, DISPLAY_AUTO = 0, 1                                      # PT_DISPLAY_* exposure modes
+class BloomParams(C.Structure):
+    """pt_bloom_params; BloomParams.default() = pt_bloom_params_default (threshold 1, strength 0.25, spread 0.75,
+    clamp 65504, levels from the size)."""
+    _fields_ = [("threshold", C.c_float), ("strength", C.c_float), ("spread", C.c_float), ("clamp", C.c_float),
+                ("levels", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    @classmethod
+    def default(cls) -> "BloomParams":
+        p = cls()
+        lib().pt_bloom_params_default(C.byref(p))
+        return p
+
+
 DISPLAY_NONE, DISPLAY_REINHARD, DISPLAY_ACES, DISPLAY_HABLE = 0, 1, 2, 3  # curves
 DISPLAY_LINEAR, DISPLAY_SRGB = 0, 1                                      # transfers
-assert C.sizeof(DisplayParams) == 64
+assert C.sizeof(DisplayParams) == 64 and C.sizeof(BloomParams) == 32
 assert C.sizeof(DenoiseParams) == 32 and C.sizeof(DenoiseVarParams) == 32 and C.sizeof(TemporalParams) == 32
 assert C.sizeof(AdaptiveParams) == 32
 assert C.sizeof(Geom) == 272 and C.sizeof(Material) == 48 and C.sizeof(Triangle) == 124
@@ -456,6 +469,13 @@ SIGNATURES = {
     "pt_display_info": (_I, [_P, _P, _IP, _FP, _IP]),
     "pt_display_tables": (None, [_P, _P, _FP]),
     "pt_preview_display": (_I, [_P, _I, _P, _P, _I, _P]),
+    "pt_bloom_params_default": (None, [C.POINTER(BloomParams)]),
+    "pt_bloom_create": (_I, [_I, _I, C.POINTER(BloomParams), C.POINTER(_P)]),
+    "pt_bloom_destroy": (_I, [_P]),
+    "pt_bloom_apply": (_I, [_P, _P, _F, _P, _P]),
+    "pt_bloom_host": (_I, [_I, _I, _P, _F, C.POINTER(BloomParams), _P]),
+    "pt_bloom_info": (_I, [_P, _IP, _IP, _IP]),
+    "pt_preview_bloom": (_I, [_P, _I, _P, _P, _P]),
     "pt_env_params_default": (None, [C.POINTER(EnvParams)]),
     "pt_scene_set_environment": (_I, [_P, _I, _I, _P, C.POINTER(EnvParams)]),
     "pt_scene_set_environment_octa": (_I, [_P, _I, _P, C.POINTER(EnvParams)]),
@@ -491,8 +511,11 @@ def _preload_torch() -> None:
 # pt_jpeg_*, pt_preview_jpeg: the A/B against the build before the JPEG encoder; pt_png_*, pt_preview_png: the
 # A/B against the build before the PNG encoder; pt_hdr_*, pt_preview_hdr: the A/B against the build before the
 # HDR encoder; pt_exr_*, pt_preview_exr: the A/B against the build before the OpenEXR encoder; pt_display_*, pt_preview_display: scripts/display_time.py's A/B against the build before the display
-# transform; pt_env_*, pt_scene_*_environment*, pt_decode_hdr: the A/B against the build before the environment).
-_OPTIONAL = {"pt_env_params_default", "pt_scene_set_environment", "pt_scene_set_environment_octa",
+# transform; pt_env_*, pt_scene_*_environment*, pt_decode_hdr: the A/B against the build before the environment;
+# pt_bloom_*, pt_preview_bloom: the A/B against the build before the bloom).
+_OPTIONAL = {"pt_bloom_params_default", "pt_bloom_create", "pt_bloom_destroy", "pt_bloom_apply", "pt_bloom_host", "pt_bloom_info",
+             "pt_preview_bloom",
+             "pt_env_params_default", "pt_scene_set_environment", "pt_scene_set_environment_octa",
              "pt_scene_load_environment", "pt_scene_clear_environment", "pt_scene_get_environment", "pt_decode_hdr",
              "pt_env_eval", "pt_env_eval_host",
              "pt_selftest_math", "pt_profile_read_kinds", "pt_ctx_room_info", "pt_scene_room_info", "pt_ctx_depart_counts",

@@ -29,7 +29,7 @@ ARCH = "gfx950"
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 DEVICE_SRCS = ["sc_kernels.hip", "sc_variants.hip", "pt_kernels.hip", "bvh_build.hip", "pt_denoise.hip",
                "pt_temporal.hip", "pt_adaptive.hip", "pt_enc_common.hip", "pt_jpeg_enc.hip", "pt_png_enc.hip",
-               "pt_hdr_enc.hip", "pt_exr_enc.hip", "pt_display.hip", "pt_env.hip"]
+               "pt_hdr_enc.hip", "pt_exr_enc.hip", "pt_display.hip", "pt_env.hip", "pt_bloom.hip"]
 # pt_kernels.hip: no SLP vectorisation.  Packing independent f32 ops into v_pk_* pairs needed
 # register pairs and moves: k_bounce took 79 VGPRs (6 waves/SIMD) instead of 60 (8 waves), and
 # measured 30.8k vs 32.7k Mray/s on the bench (same box, alternating runs; same bits).

@@ -516,4 +516,20 @@ int pt_preview_display(pt_ctx* ctx, int32_t iter, pt_display* d, uint8_t* d_pix,
     return mark_ctx(c, st);
 }
 
+// ---- bloom --------------------------------------------------------------------
+// The same ordering; the output is an accumulator of `iter` samples like the input.
+int pt_preview_bloom(pt_ctx* ctx, int32_t iter, pt_bloom* b, float* d_out, void* stream) {
+    CtxHead* c = ctx_head(ctx);
+    if (!c || !b || !d_out || iter <= 0) return pt::fail(PT_ERR_ARG, "bad argument");
+    if (c->world > 1) return pt::fail(PT_ERR_ARG, "pt_preview_bloom needs the whole image (world == 1)");
+    int32_t bw = 0, bh = 0;
+    if (int rc = pt::bloom_size(b, &bw, &bh)) return rc;
+    if (bw != c->W || (int64_t)bw * bh != (int64_t)c->npix)
+        return pt::fail(PT_ERR_ARG, "the bloom and the context's tile differ in size");
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = wait_finalize(c, st)) return rc;
+    if (int rc = pt_bloom_apply(b, c->image, (float)iter, d_out, st)) return rc;
+    return mark_ctx(c, st);
+}
+
 }  // extern "C"

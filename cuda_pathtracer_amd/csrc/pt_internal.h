@@ -91,6 +91,8 @@ void enc_size(const EncHead* e, int32_t* width, int32_t* height);
 void exr_channels(const pt_exr_enc* e, const pt_exr_channel** channels, int32_t* n);
 // pt_display (pt_display.hip): the image size it was created for and whether its exposure is metered
 int display_size(const pt_display* d, int32_t* width, int32_t* height, int32_t* automatic);
+// pt_bloom (pt_bloom.hip): the image size it was created for
+int bloom_size(const pt_bloom* b, int32_t* width, int32_t* height);
 
 inline float bits_to_float(int32_t v) {
     float f;

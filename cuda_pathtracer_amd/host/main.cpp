@@ -7,6 +7,11 @@
 //                  [--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png]
 //                  [--device-hdr] [--tonemap none|reinhard|aces|hable] [--exposure EV|auto] [--srgb] [--exr] [--exr-half]
 //                  [--env FILE.hdr] [--env-scale X] [--env-rotate X,Y,Z]
+//                  [--bloom STRENGTH] [--bloom-threshold X] [--bloom-levels K]
+// --bloom, --bloom-threshold, --bloom-levels: any of them additionally writes ...samp.bloom.png, the accumulator through the
+// bloom (pt_preview_bloom, DESIGN.md §20: the glare's strength, the luminance above which a pixel glares, the pyramid's
+// levels) and then through the display transform of the display flags (without them: pt_tonemap's conversion),
+// x-mirrored and written by the device PNG encoder.  The other files keep their names and bytes.
 // --env gives the scene an environment (pt_scene_load_environment of a lat-long Radiance file; --env-scale
 // multiplies its radiance, --env-rotate turns it by degrees about x, y, z); a scene file's own Extensions.ENVIRONMENT is replaced.
 // --exr additionally writes ...samp.exr, an OpenEXR file written on the device (pt_preview_exr, DESIGN.md §18: FLOAT, ZIP,
@@ -189,6 +194,45 @@ std::string saveDisplayDevice(const Scene& scene, const std::string& dir, const 
     return filename;
 }
 
+// --bloom: ...samp.bloom.png, the accumulator through the bloom (pt_preview_bloom) into a device buffer, that buffer
+// through the display transform (the display flags', or the defaults: pt_tonemap's conversion) and the device PNG encoder.
+std::string saveBloomDevice(const Scene& scene, const std::string& dir, const std::string& start, int iteration,
+                            const pt_bloom_params& bprm, const pt_display_params& dprm) {
+    const int W = scene.state.camera.res[0], H = scene.state.camera.res[1];
+    auto die = [](const char* what) {
+        std::fprintf(stderr, "saveImage (bloom): %s: %s\n", what, pt_last_error());
+        std::exit(EXIT_FAILURE);
+    };
+    pt_bloom* bloom = nullptr;
+    if (pt_bloom_create(W, H, &bprm, &bloom)) die("bloom");
+    pt_display* disp = nullptr;
+    if (pt_display_create(W, H, &dprm, &disp)) die("display transform");
+    pt_png_params prm;
+    pt_png_params_default(&prm);   // (no mirror: the display transform's bytes are mirrored already)
+    pt_png_enc* enc = nullptr;
+    if (pt_png_enc_create(W, H, &prm, &enc)) die("encoder");
+    float* d_rgb = nullptr;
+    uint8_t* d_pix = nullptr;
+    if (hipMalloc((void**)&d_rgb, (size_t)W * H * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&d_pix, (size_t)W * H * 3) != hipSuccess) {
+        std::fprintf(stderr, "saveImage (bloom): out of device memory\n");
+        std::exit(EXIT_FAILURE);
+    }
+    if (pt_preview_bloom(pathtraceContext(), iteration, bloom, d_rgb, nullptr)) die("pt_preview_bloom");
+    if (dprm.exposure_mode == PT_DISPLAY_AUTO ? pt_display_frame(disp, d_rgb, (float)iteration, d_pix, 3, nullptr)
+                                              : pt_display_apply(disp, d_rgb, (float)iteration, d_pix, 3, nullptr))
+        die("display transform");
+    const std::string filename = saveDeviceFile(scene, dir, start, iteration, ".bloom.png", pt_png_enc_bound(enc),
+                                                [&](uint8_t* d_out, int64_t cap, int64_t* d_size) {
+        return pt_png_enc_pixels(enc, d_pix, 3, d_out, cap, d_size, nullptr);
+    });
+    pt_png_enc_destroy(enc);
+    pt_display_destroy(disp);
+    pt_bloom_destroy(bloom);
+    (void)hipFree(d_pix);
+    (void)hipFree(d_rgb);
+    return filename;
+}
+
 void writeFloats(const std::string& path, const std::vector<float>& v) {
     FILE* f = std::fopen(path.c_str(), "wb");
     if (!f || std::fwrite(v.data(), sizeof(float), v.size(), f) != v.size() || std::fclose(f)) {
@@ -296,7 +340,8 @@ int main(int argc, char** argv) {
         std::printf("Usage: %s SCENEFILE.json [--iterations N] [--out DIR] [--sort] [--no-png] [--hdr] [--denoise] "
                     "[--denoise-variance] [--aov DIR] [--adaptive THRESHOLD] [--adaptive-every K] [--device-png] [--device-hdr] "
                     "[--tonemap none|reinhard|aces|hable] [--exposure EV|auto] [--srgb] [--exr] [--exr-half] "
-                    "[--env FILE.hdr] [--env-scale X] [--env-rotate X,Y,Z]\n", argv[0]);
+                    "[--env FILE.hdr] [--env-scale X] [--env-rotate X,Y,Z] "
+                    "[--bloom STRENGTH] [--bloom-threshold X] [--bloom-levels K]\n", argv[0]);
         return 1;
     }
     const char* sceneFile = argv[1];
@@ -310,6 +355,9 @@ int main(int argc, char** argv) {
     pt_display_params dprm;
     pt_display_params_default(&dprm);
     dprm.mirror_x = 1;
+    bool bloom = false;
+    pt_bloom_params bprm;
+    pt_bloom_params_default(&bprm);
     const char* env_file = nullptr;   // --env: a lat-long Radiance .hdr file as the scene's environment (pt_scene_load_environment)
     pt_env_params eprm;
     pt_env_params_default(&eprm);
@@ -366,6 +414,24 @@ int main(int argc, char** argv) {
         } else if (!std::strcmp(argv[i], "--srgb")) {
             dprm.transfer = PT_DISPLAY_SRGB;
             display = true;
+        } else if ((!std::strcmp(argv[i], "--bloom") || !std::strcmp(argv[i], "--bloom-threshold")) && i + 1 < argc) {
+            const bool strength = !std::strcmp(argv[i], "--bloom");
+            char* end = nullptr;
+            ++i;
+            const double v = std::strtod(argv[i], &end);
+            if (end == argv[i] || *end || !(v >= 0.0 && v <= 3.0e38)) {
+                std::fprintf(stderr, "%s %s: a number >= 0\n", argv[i - 1], argv[i]);
+                return 1;
+            }
+            (strength ? bprm.strength : bprm.threshold) = (float)v;
+            bloom = true;
+        } else if (!std::strcmp(argv[i], "--bloom-levels") && i + 1 < argc) {
+            bprm.levels = std::atoi(argv[++i]);
+            if (bprm.levels < 0 || bprm.levels > 12) {
+                std::fprintf(stderr, "--bloom-levels %s: 1 .. 12, or 0 for the size's own\n", argv[i]);
+                return 1;
+            }
+            bloom = true;
         }
         else {
             std::fprintf(stderr, "unknown argument %s\n", argv[i]);
@@ -383,6 +449,10 @@ int main(int argc, char** argv) {
     InitDataContainer(guiData);
     const int total = iterations > 0 ? iterations : (int)scene->state.iterations;
 
+    if (adaptive && bloom) {   // (runAdaptive writes its own files: the flags would be ignored)
+        std::fprintf(stderr, "--bloom, --bloom-threshold and --bloom-levels cannot be combined with --adaptive\n");
+        return 1;
+    }
     pathtraceInit(scene);
     if (adaptive) return runAdaptive(*scene, sceneFile, total, adaptive_threshold, adaptive_every, out_dir, startTimeString,
                                      png, hdr, denoise_var);
@@ -412,6 +482,7 @@ int main(int argc, char** argv) {
         std::printf("wrote %s\n", device_hdr ? saveHdrDevice(*scene, out_dir, startTimeString, iteration).c_str()
                                              : saveImage(*scene, out_dir, startTimeString, iteration, true).c_str());
     if (display) std::printf("wrote %s\n", saveDisplayDevice(*scene, out_dir, startTimeString, iteration, dprm).c_str());
+    if (bloom) std::printf("wrote %s\n", saveBloomDevice(*scene, out_dir, startTimeString, iteration, bprm, dprm).c_str());
     if (exr)
         std::printf("wrote %s\n", saveExrDevice(*scene, out_dir, startTimeString, iteration, aov ? PT_EXR_ALL_LAYERS : PT_EXR_BEAUTY,
                                                 exr_half ? PT_EXR_ALL_LAYERS : 0).c_str());

@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from ._native import (AdaptiveParams, DenoiseParams, DenoiseVarParams, DisplayParams, EnvParams, ExrChannel, ExrParams, HdrParams,  # noqa: F401
+from ._native import (AdaptiveParams, BloomParams, DenoiseParams, DenoiseVarParams, DisplayParams, EnvParams, ExrChannel, ExrParams, HdrParams,  # noqa: F401
                       JpegParams, PngParams, TemporalParams, check_pt, lib)
 
 SPHERE, CUBE, MESH = 0, 1, 2
@@ -539,33 +539,67 @@ class PathTracer:
         check_pt(entry(self._h, int(iteration), encoder._h, out.data_ptr(), encoder.cap, size.data_ptr(), _stream_ptr(stream)))
         return encoder._read(stream)
 
+    def preview_bloom(self, iteration: int, bloom: "Bloom", dst_ptr: "int | None" = None, stream=None):
+        """The accumulated image of `iteration` iterations through `bloom` (pt_preview_bloom), still an
+        accumulator of that many samples: as floats at the device pointer dst_ptr, asynchronous; or without one into
+        the device buffer `bloom` keeps and returned as a (rows, width, 3) float32 array."""
+        ptr = bloom._buffer().data_ptr() if dst_ptr is None else int(dst_ptr)
+        check_pt(lib().pt_preview_bloom(self._h, int(iteration), bloom._h, C.c_void_p(ptr), _stream_ptr(stream)))
+        if dst_ptr is not None:
+            return None
+        bloom._wait(stream)
+        return bloom._buffer().cpu().numpy()
+
+    def _bloomed(self, iteration: int, bloom: "Bloom", stream, reader) -> int:
+        """preview_bloom into the device buffer `bloom` keeps: the pointer of an accumulator of `iteration` samples for
+        `reader` (a DisplayTransform or an encoder), which reads an image of its own size from it."""
+        if (reader.width, reader.height) != (bloom.width, bloom.height):
+            raise ValueError(f"bloom= is for {bloom.width} x {bloom.height} images, {type(reader).__name__} for "
+                             f"{reader.width} x {reader.height}")
+        ptr = bloom._buffer().data_ptr()
+        self.preview_bloom(iteration, bloom, ptr, stream)
+        return ptr
+
     def preview_display(self, iteration: int, display: "DisplayTransform", dst_ptr: int, pixel_stride: int = 4,
-                        stream=None) -> None:
+                        stream=None, bloom: "Bloom | None" = None) -> None:
         """The accumulated image of `iteration` iterations through `display` (pt_preview_display: metered first in
-        auto mode) as RGB8 / RGBA8 bytes at the device pointer dst_ptr; asynchronous."""
+        auto mode) as RGB8 / RGBA8 bytes at the device pointer dst_ptr; asynchronous.  bloom: a Bloom the image goes
+        through first, into the device buffer it keeps."""
+        if bloom is not None:
+            entry = lib().pt_display_frame if display.automatic else lib().pt_display_apply
+            check_pt(entry(display._h, C.c_void_p(self._bloomed(iteration, bloom, stream, display)), float(iteration), C.c_void_p(dst_ptr),
+                           int(pixel_stride), _stream_ptr(stream)))
+            return
         check_pt(lib().pt_preview_display(self._h, int(iteration), display._h, C.c_void_p(dst_ptr), int(pixel_stride),
                                           _stream_ptr(stream)))
 
-    def _preview_displayed(self, iteration: int, encoder: "_Encoder", display: "DisplayTransform", stream) -> bytes:
+    def _preview_displayed(self, iteration: int, encoder: "_Encoder", display: "DisplayTransform", stream, bloom=None) -> bytes:
         """preview_display into the device pixels `encoder` keeps, then its pixels entry: only the file crosses."""
         pix = encoder._pixel_buffer()
-        self.preview_display(iteration, display, pix.data_ptr(), 4, stream)
+        self.preview_display(iteration, display, pix.data_ptr(), 4, stream, bloom=bloom)
         return encoder.encode(pix.data_ptr(), pixel_stride=4, stream=stream)
 
-    def preview_jpeg(self, iteration: int, encoder: "JpegEncoder", stream=None, display: "DisplayTransform | None" = None) -> bytes:
+    def preview_jpeg(self, iteration: int, encoder: "JpegEncoder", stream=None, display: "DisplayTransform | None" = None,
+                     bloom: "Bloom | None" = None) -> bytes:
         """The accumulated image of `iteration` iterations as preview_rgba converts it, as a JPEG file
         encoded on the device by `encoder` (pt_preview_jpeg): only the file crosses to the host.  display: a
-        DisplayTransform that converts it instead, still on the device."""
+        DisplayTransform that converts it instead, still on the device.  bloom: a Bloom the image goes
+        through first, into the device buffer it keeps; the encoder's accumulator entry follows."""
         if display is not None:
-            return self._preview_displayed(iteration, encoder, display, stream)
+            return self._preview_displayed(iteration, encoder, display, stream, bloom)
+        if bloom is not None:
+            return encoder.encode(self._bloomed(iteration, bloom, stream, encoder), samples=float(iteration), stream=stream)
         return self._preview_file(lib().pt_preview_jpeg, iteration, encoder, stream)
 
-    def preview_png(self, iteration: int, encoder: "PngEncoder", stream=None, display: "DisplayTransform | None" = None) -> bytes:
+    def preview_png(self, iteration: int, encoder: "PngEncoder", stream=None, display: "DisplayTransform | None" = None,
+                    bloom: "Bloom | None" = None) -> bytes:
         """The accumulated image of `iteration` iterations as a PNG file written on the device by `encoder`
         (pt_preview_png), converted as the encoder's params.conv says: only the file crosses to the host.  display:
-        a DisplayTransform that converts it instead, still on the device."""
+        a DisplayTransform that converts it instead, still on the device.  bloom: as preview_jpeg's."""
         if display is not None:
-            return self._preview_displayed(iteration, encoder, display, stream)
+            return self._preview_displayed(iteration, encoder, display, stream, bloom)
+        if bloom is not None:
+            return encoder.encode(self._bloomed(iteration, bloom, stream, encoder), samples=float(iteration), stream=stream)
         return self._preview_file(lib().pt_preview_png, iteration, encoder, stream)
 
     def save_png(self, path: str, iteration: int) -> str:
@@ -582,42 +616,52 @@ class PathTracer:
             f.write(data)
         return str(path)
 
-    def preview_hdr(self, iteration: int, encoder: "HdrEncoder", stream=None) -> bytes:
+    def preview_hdr(self, iteration: int, encoder: "HdrEncoder", stream=None, bloom: "Bloom | None" = None) -> bytes:
         """The accumulated image of `iteration` iterations as a Radiance HDR file written on the device by
-        `encoder` (pt_preview_hdr): only the file crosses to the host."""
+        `encoder` (pt_preview_hdr): only the file crosses to the host.  bloom: a Bloom the image goes through first
+        (DESIGN.md §20), into the device buffer it keeps."""
+        if bloom is not None:
+            return encoder.encode(self._bloomed(iteration, bloom, stream, encoder), float(iteration), stream=stream)
         return self._preview_file(lib().pt_preview_hdr, iteration, encoder, stream)
 
-    def save_hdr(self, path: str, iteration: int) -> str:
+    def save_hdr(self, path: str, iteration: int, bloom: "Bloom | None" = None) -> str:
         """save_image_hdr's file (x-mirrored, accumulator / iteration) written on the device, without the
-        accumulator crossing to the host."""
+        accumulator crossing to the host.  bloom: as preview_hdr's."""
         prm = N.HdrParams.default()
         prm.mirror_x = 1
         enc = HdrEncoder(self.width, self.rows, prm)
         try:
-            data = self.preview_hdr(iteration, enc)
+            data = self.preview_hdr(iteration, enc, bloom=bloom)
         finally:
             enc.free()
         with open(path, "wb") as f:
             f.write(data)
         return str(path)
 
-    def preview_exr(self, iteration: int, encoder: "ExrEncoder", layers: int = N.EXR_BEAUTY, stream=None) -> bytes:
+    def preview_exr(self, iteration: int, encoder: "ExrEncoder", layers: int = N.EXR_BEAUTY, stream=None,
+                    bloom: "Bloom | None" = None) -> bytes:
         """The layers `layers` (a mask of EXR_BEAUTY .. EXR_ID) as one OpenEXR file written on the device by `encoder`
         (pt_preview_exr), whose channels must be exr_ctx_channels(layers, half)'s: the accumulated image of `iteration`
-        iterations and the first-hit planes.  Only the file crosses to the host."""
+        iterations and the first-hit planes.  Only the file crosses to the host.  bloom: a Bloom the image goes through
+        first, into the device buffer it keeps; the beauty layer alone (ValueError otherwise)."""
+        if bloom is not None:
+            if int(layers) != N.EXR_BEAUTY:
+                raise ValueError("preview_exr: bloom= takes the beauty layer alone")
+            ptr = self._bloomed(iteration, bloom, stream, encoder)
+            return encoder.encode([ptr, ptr + 4, ptr + 8], strides=[3] * 3, divisors=[float(iteration)] * 3, stream=stream)
         out, size = encoder._buffers()
         check_pt(lib().pt_preview_exr(self._h, int(iteration), int(layers), encoder._h, out.data_ptr(), encoder.cap,
                                       size.data_ptr(), _stream_ptr(stream)))
         return encoder._read(stream)
 
-    def save_exr(self, path: str, iteration: int, layers: int = N.EXR_BEAUTY, half: int = 0) -> str:
+    def save_exr(self, path: str, iteration: int, layers: int = N.EXR_BEAUTY, half: int = 0, bloom: "Bloom | None" = None) -> str:
         """The layers as a ZIP-compressed OpenEXR file, x-mirrored like every saved image, written on the device; the
-        layers of `half` that may be are stored as HALF."""
+        layers of `half` that may be are stored as HALF.  bloom: as preview_exr's."""
         prm = N.ExrParams.default()
         prm.mirror_x = 1
         enc = ExrEncoder(self.width, self.rows, exr_ctx_channels(layers, half), prm)
         try:
-            data = self.preview_exr(iteration, enc, layers)
+            data = self.preview_exr(iteration, enc, layers, bloom=bloom)
         finally:
             enc.free()
         with open(path, "wb") as f:
@@ -1166,6 +1210,7 @@ class DisplayTransform:
         self.width, self.height = int(width), int(height)
         self._h = C.c_void_p()
         prm = params if params is not None else N.DisplayParams.default()
+        self.automatic = prm.exposure_mode == N.DISPLAY_AUTO
         check_pt(lib().pt_display_create(self.width, self.height, C.byref(prm), C.byref(self._h)))
 
     def free(self) -> None:
@@ -1257,6 +1302,73 @@ def display_transform(acc: np.ndarray, samples: float, params: "N.DisplayParams 
     out = np.empty((img.shape[0], img.shape[1], int(pixel_stride)), np.uint8)
     check_pt(lib().pt_display_host(img.shape[1], img.shape[0], img.ctypes.data, float(samples), C.byref(prm), out.ctypes.data,
                                    int(pixel_stride)))
+    return out
+
+
+class Bloom:
+    """pt_bloom: bloom on the device for (height, width) accumulators; params: a BloomParams (default:
+    threshold 1, strength 0.25, spread 0.75, levels from the size).  apply takes an (H, W, 3) float32 array or tensor
+    of `samples` samples, or a device pointer (int) to one; its output is an accumulator of as many samples."""
+
+    def __init__(self, width: int, height: int, params: "N.BloomParams | None" = None):
+        self.width, self.height = int(width), int(height)
+        self._h = C.c_void_p()
+        self._buf = None
+        prm = params if params is not None else N.BloomParams.default()
+        check_pt(lib().pt_bloom_create(self.width, self.height, C.byref(prm), C.byref(self._h)))
+
+    def free(self) -> None:
+        if self._h is not None and self._h.value:
+            check_pt(lib().pt_bloom_destroy(self._h))
+        self._h = None
+        self._buf = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    _source, _wait = DisplayTransform._source, DisplayTransform._wait
+
+    def _buffer(self):
+        """The device accumulator the object keeps for its output (PathTracer's bloom= arguments)."""
+        import torch
+        if self._buf is None:
+            self._buf = torch.empty((self.height, self.width, 3), dtype=torch.float32, device="cuda")
+        return self._buf
+
+    def apply(self, src, samples: float, dst_ptr: "int | None" = None, stream=None):
+        """pt_bloom_apply: the floats to the device pointer dst_ptr (asynchronous when src is a pointer too; dst_ptr
+        may be src's), or without one returned as an (H, W, 3) float32 array."""
+        import torch
+        ptr, keep = self._source(src)
+        out = None
+        if dst_ptr is None:
+            out = torch.empty((self.height, self.width, 3), dtype=torch.float32, device="cuda")
+            dst_ptr = out.data_ptr()
+        check_pt(lib().pt_bloom_apply(self._h, C.c_void_p(ptr), float(samples), C.c_void_p(int(dst_ptr)), _stream_ptr(stream)))
+        if out is None and keep is None:
+            return None   # (device to device: asynchronous)
+        self._wait(stream)
+        return out.cpu().numpy() if out is not None else None
+
+    def info(self) -> dict:
+        """pt_bloom_info (no device): levels (K) and the widths and heights of the levels 1 .. K."""
+        k, w, h = C.c_int32(), (C.c_int32 * 12)(), (C.c_int32 * 12)()
+        check_pt(lib().pt_bloom_info(self._h, C.byref(k), w, h))
+        return {"levels": int(k.value), "widths": [int(v) for v in w[:k.value]], "heights": [int(v) for v in h[:k.value]]}
+
+
+def bloom(acc: np.ndarray, samples: float, params: "N.BloomParams | None" = None) -> np.ndarray:
+    """An (H, W, 3) float32 host accumulator of `samples` samples through the bloom on the device (pt_bloom_host) ->
+    (H, W, 3) float32, an accumulator of as many samples."""
+    img = np.ascontiguousarray(acc, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"image shape {img.shape}: expected (H, W, 3)")
+    prm = params if params is not None else N.BloomParams.default()
+    out = np.empty_like(img)
+    check_pt(lib().pt_bloom_host(img.shape[1], img.shape[0], img.ctypes.data, float(samples), C.byref(prm), out.ctypes.data))
     return out
 
 

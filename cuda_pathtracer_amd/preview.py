@@ -42,9 +42,10 @@ from pathlib import Path
 import numpy as np
 
 from . import _native as N
-from .pathtrace import (DenoiseVarParams, DisplayParams, DisplayTransform, GuiDataContainer, HdrEncoder, HdrParams, JpegEncoder,
+from .pathtrace import (Bloom, BloomParams, DenoiseVarParams, DisplayParams, DisplayTransform, GuiDataContainer, HdrEncoder, HdrParams, JpegEncoder,
                         PathTracer, PngEncoder, Scene, TemporalHistory, _jpeg_params, _png_params, display_transform, encode_jpeg,
                         encode_png, save_image, tonemap)
+from .pathtrace import bloom as bloom_host
 
 F32 = np.float32
 PI = F32(3.1415926535897932384626422832795028841971)   # utilities.h PI (a float)
@@ -59,6 +60,8 @@ SLIDERS = {"aperture": (0.1, 1.0), "focal_len": (10.0, 80.0)}   # ImGui::SliderF
 # panel settings of the display transform: display only, like `denoise`
 TONEMAPS = {"none": N.DISPLAY_NONE, "reinhard": N.DISPLAY_REINHARD, "aces": N.DISPLAY_ACES, "hable": N.DISPLAY_HABLE}
 EXPOSURE_EV = (-16.0, 16.0)
+# panel settings of the bloom: display only too; strength 0 is off
+BLOOM_STRENGTH, BLOOM_THRESHOLD = (0.0, 4.0), (0.0, 65504.0)
 AUTO_EXPOSURE_RATE = 32   # of 256: the share of the way to the metered target a frame goes
 
 
@@ -89,7 +92,12 @@ class PreviewSession:
     (pt_preview_display, into the encoders' pixel entries in JPEG mode and with png_device), denoised and temporal
     frames through display_transform on their host arrays.  With auto_exposure the exposure is metered every frame
     and adapts over frames (exposure_ev is then the compensation).  With all four at their defaults every path is
-    the one described above."""
+    the one described above.
+
+    bloom, bloom_threshold (panel settings; bloom is the glare's strength, 0 and off by default): the frames go
+    through the session's Bloom first and then through the DisplayTransform, which then also runs
+    at its defaults: raw frames on the device (the bloom= of preview_display, preview_jpeg and preview_png), denoised
+    and temporal frames through bloom() on their host arrays."""
 
     def __init__(self, scene: Scene, gui: GuiDataContainer | None = None, out_dir: str | None = None,
                  tracer_factory=None, read_preview=None, history_factory=None, jpeg: int | None = None,
@@ -147,6 +155,8 @@ class PreviewSession:
         self._hdr_enc = None         # /frame.hdr's encoder, made at the first request
         self.tonemap, self.exposure_ev, self.auto_exposure, self.srgb = "none", 0.0, False, False
         self._display = None         # the session's DisplayTransform, made when a frame needs it
+        self.bloom, self.bloom_threshold = 0.0, 1.0
+        self._bloom = None           # the session's Bloom, likewise
         self._raw_frame = False      # the current frame is the context's accumulator as pt_preview_rgba converts it
         self.jpeg_bytes = b""        # the current frame's file (JPEG mode)
         self.frame_serial = 0        # counts the files: /stream.mjpg sends each once
@@ -229,6 +239,13 @@ class PreviewSession:
                 self._set_display(exposure_ev=ev)
             elif name in ("auto_exposure", "srgb"):
                 self._set_display(**{name: bool(value)})
+            elif name in ("bloom", "bloom_threshold"):   # display only as well
+                lo, hi = BLOOM_STRENGTH if name == "bloom" else BLOOM_THRESHOLD
+                if isinstance(value, (bool, str)) or value is None or not lo <= float(value) <= hi:   # (false for NaN)
+                    raise ValueError(f"{name} {value!r}: a number in {lo} .. {hi}")
+                if getattr(self, name) != float(value):
+                    setattr(self, name, float(value))
+                    self._free_bloom()   # (its parameters are fixed at creation: the next frame makes another)
             elif name in GENERAL_SETTINGS or name in ("SSAA", "DoF"):
                 if name == "sortbyMaterial" and value and self.scene.environment() is not None:
                     # (pt_set_flags would refuse it inside the render loop and end the session: refused here instead)
@@ -250,7 +267,7 @@ class PreviewSession:
             self._free_display()   # (its parameters are fixed at creation: the next frame makes another)
 
     def _display_on(self) -> bool:
-        return self.tonemap != "none" or self.exposure_ev != 0.0 or self.auto_exposure or self.srgb
+        return self.tonemap != "none" or self.exposure_ev != 0.0 or self.auto_exposure or self.srgb or self.bloom > 0.0
 
     def _display_params(self) -> DisplayParams:
         """The bytes land in the PBO's orientation (the encoders and display_rgb mirror x)."""
@@ -266,6 +283,25 @@ class PreviewSession:
         if self._display is None:
             self._display = DisplayTransform(self.width, self.height, self._display_params())
         return self._display
+
+    # ---- the bloom ------------------------------------------------------------
+    def _bloom_params(self) -> BloomParams:
+        p = BloomParams.default()
+        p.strength, p.threshold = self.bloom, self.bloom_threshold
+        return p
+
+    def _bloom_obj(self) -> "Bloom | None":
+        """The bloom= of the context's preview methods: None while the strength is 0."""
+        if not self.bloom > 0.0:
+            return None
+        if self._bloom is None:
+            self._bloom = Bloom(self.width, self.height, self._bloom_params())
+        return self._bloom
+
+    def _free_bloom(self) -> None:
+        if self._bloom is not None:
+            self._bloom.free()
+            self._bloom = None
 
     def _free_display(self) -> None:
         if self._display is not None:
@@ -337,7 +373,7 @@ class PreviewSession:
         if self._dbuf is None:
             self._dbuf = torch.empty((self.height, self.width, 4), dtype=torch.uint8, device="cuda")
         if self._display_on():
-            ctx.preview_display(it, self._display_obj(), self._dbuf.data_ptr(), 4)
+            ctx.preview_display(it, self._display_obj(), self._dbuf.data_ptr(), 4, bloom=self._bloom_obj())
         else:
             ctx.preview_rgba(it, self._dbuf.data_ptr())   # (the render's stream: NULL)
         return self._dbuf.cpu().numpy()
@@ -346,7 +382,7 @@ class PreviewSession:
         if self._enc is None:
             self._enc = JpegEncoder(self.width, self.height, _jpeg_params(self.jpeg, "420", True))
         if self._display_on():
-            return self.ctx.preview_jpeg(self.iteration, self._enc, display=self._display_obj())
+            return self.ctx.preview_jpeg(self.iteration, self._enc, display=self._display_obj(), bloom=self._bloom_obj())
         return self.ctx.preview_jpeg(self.iteration, self._enc)
 
     def png_frame(self) -> bytes:
@@ -358,7 +394,7 @@ class PreviewSession:
                 if self._png_enc is None:
                     self._png_enc = PngEncoder(self.width, self.height, _png_params(mirror_x=True))
                 if self._display_on():
-                    return self.ctx.preview_png(self.iteration, self._png_enc, display=self._display_obj())
+                    return self.ctx.preview_png(self.iteration, self._png_enc, display=self._display_obj(), bloom=self._bloom_obj())
                 return self.ctx.preview_png(self.iteration, self._png_enc)
             self._current_rgba()
             return encode_png(self.rgba, mirror_x=True)
@@ -395,6 +431,8 @@ class PreviewSession:
     def _pbo_of(self, img: np.ndarray) -> np.ndarray:
         self._rgba_current = True
         self._raw_frame = False
+        if self.bloom > 0.0:
+            img = bloom_host(img, 1.0, self._bloom_params())
         rgb = display_transform(img, 1.0, self._display_params()) if self._display_on() else tonemap(img, 1.0)[:, ::-1]
         out = np.zeros((self.height, self.width, 4), np.uint8)
         out[..., :3] = rgb
@@ -454,6 +492,7 @@ class PreviewSession:
                 self._hdr_enc.free()
                 self._hdr_enc = None
             self._free_display()
+            self._free_bloom()
             self.frame_ready.notify_all()
 
     # ---- what the window shows ----------------------------------------------------------------
@@ -480,7 +519,8 @@ class PreviewSession:
                 "settings": {**{k: getattr(self.gui, k) for k in GENERAL_SETTINGS + VISUAL_SETTINGS},
                              "denoise": self.denoise, "denoise_variance": self.denoise_variance,
                              "denoise_temporal": self.denoise_temporal, "tonemap": self.tonemap,
-                             "exposure_ev": self.exposure_ev, "auto_exposure": self.auto_exposure, "srgb": self.srgb},
+                             "exposure_ev": self.exposure_ev, "auto_exposure": self.auto_exposure, "srgb": self.srgb,
+                             "bloom": self.bloom, "bloom_threshold": self.bloom_threshold},
                 "camera": {"phi": float(self.phi), "theta": float(self.theta), "zoom": float(self.zoom),
                            "look_at": [float(v) for v in self.look_at],
                            "position": [float(v) for v in cam.position[:3]]},
@@ -532,7 +572,9 @@ fieldset{border:1px solid #555;margin:0 0 8px 0} input[type=range]{width:160px}<
 <label>Tone curve <select id="tonemap"><option>none</option><option>reinhard</option><option>aces</option><option>hable</option></select></label><br>
 <label>Exposure (stops) <input type="range" id="exposure_ev" min="-8" max="8" step="0.25"></label><br>
 <label><input type="checkbox" id="auto_exposure"> Meter the exposure (the slider compensates)</label><br>
-<label><input type="checkbox" id="srgb"> sRGB transfer</label></fieldset>
+<label><input type="checkbox" id="srgb"> sRGB transfer</label><br>
+<label>Bloom strength <input type="range" id="bloom" min="0" max="2" step="0.05"></label><br>
+<label>Bloom threshold <input type="range" id="bloom_threshold" min="0" max="8" step="0.1"></label></fieldset>
 <fieldset><legend>Visual settings</legend>
 <label><input type="checkbox" id="SSAA"> Enable stochastic sampled antialiasing</label><br>
 <label><input type="checkbox" id="DoF"> Enable DoF effects</label><br>
@@ -554,7 +596,7 @@ window.addEventListener('keydown',e=>{const k=e.key==='Escape'?'ESCAPE':e.key===
 for(const id of ['russianRoulette','sortbyMaterial','useThrustPartition','denoise','denoise_variance','denoise_temporal','SSAA','DoF','auto_exposure','srgb'])
  document.getElementById(id).addEventListener('change',e=>post({kind:'setting',name:id,value:e.target.checked}));
 document.getElementById('tonemap').addEventListener('change',e=>post({kind:'setting',name:'tonemap',value:e.target.value}));
-for(const id of ['aperture','focal_len','exposure_ev'])
+for(const id of ['aperture','focal_len','exposure_ev','bloom','bloom_threshold'])
  document.getElementById(id).addEventListener('input',e=>post({kind:'setting',name:id,value:parseFloat(e.target.value)}));
 async function poll(){try{const s=await (await fetch('/state')).json();
  document.getElementById('title').textContent=s.title;document.title=s.title;

@@ -1041,6 +1041,39 @@ void pt_display_tables(float srgb[256], float pow2[256], float* hable_white);
 int pt_preview_display(pt_ctx* c, int32_t iter, pt_display* d, uint8_t* d_pix, int32_t pixel_stride,
                        void* stream);
 
+/* ---- bloom on the device ------------------------------------------------------- */
+/* The float accumulator plus its glare, in the accumulator's own unit: a bright pass, a pyramid of K levels
+ * through the binomial [1 3 3 1]/8, a 2x tent on the way back up, and out = v + glare * samples.  The output
+ * is an exact function of the input floats (DESIGN.md §20 is the definition; tests/bloom_ref.py restates it
+ * in numpy).  It feeds whatever takes an accumulator: pt_display_*, the encoders' accum entries.  The object
+ * needs no context; pt_bloom_create touches no device (argument errors, PT_ERR_ARG, are found before any
+ * device call), the pyramid is allocated at first use, and later calls neither allocate nor synchronise. */
+typedef struct pt_bloom_params {
+    float threshold;   /* luminance above which a pixel glares, finite and >= 0, default 1 */
+    float strength;    /* the glare's weight in the output, finite and >= 0, default 0.25 */
+    float spread;      /* the weight of each coarser level relative to the finer, 0 < spread <= 1, default 0.75 */
+    float clamp;       /* per-channel ceiling of the bright pass, 0 < clamp <= 65504, default 65504 */
+    int32_t levels;    /* default 0: K = clamp(floor(log2(min(width, height))), 1, 6); else K, 1 .. 12 */
+    int32_t reserved[3];
+} pt_bloom_params;
+void pt_bloom_params_default(pt_bloom_params* p);
+typedef struct pt_bloom pt_bloom;
+int pt_bloom_create(int32_t width, int32_t height, const pt_bloom_params* p, pt_bloom** out);
+int pt_bloom_destroy(pt_bloom* b);
+/* Asynchronous on `stream`, device pointers aligned to 4 bytes (the caller orders the calls of one object);
+ * nothing waits for the host.  d_rgb: the float accumulator of `samples` samples (finite, > 0); d_out: as many
+ * floats, d_rgb itself (in place) or memory that does not overlap it (PT_ERR_ARG otherwise). */
+int pt_bloom_apply(pt_bloom* b, const float* d_rgb, float samples, float* d_out, void* stream);
+/* Host arrays, synchronous: one object made, used and destroyed. */
+int pt_bloom_host(int32_t width, int32_t height, const float* rgb, float samples, const pt_bloom_params* p,
+                  float* out);
+/* The K in use and the sizes of the levels 1 .. K (the other entries 0); no device.  Any pointer may be NULL. */
+int pt_bloom_info(pt_bloom* b, int32_t* levels, int32_t widths[12], int32_t heights[12]);
+/* The context's accumulated image of `iter` iterations through `b` into the caller's device buffer of as many
+ * floats.  b's size must be the tile's and world must be 1 (PT_ERR_ARG otherwise).  Orders itself like
+ * pt_preview_rgba. */
+int pt_preview_bloom(pt_ctx* c, int32_t iter, pt_bloom* b, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
